@@ -11,6 +11,11 @@ Workload = BASELINE.json configs[1]: 10 000 pairs x 2 000 correspondences per GP
 Launch  : python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
          python -m torch.distributed.run --nproc-per-node N ... (one rank per GPU).
 Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints the line (contract keys, `config`, the HBM roofline of the
+timed kernel from the timed steps' own HIP events).  --full adds every other leg: quality against the ground truth, the
+replayed PMC profile, SURVEY 8d's variants, the graph-level configs 3 / 4 / 5, the secondary kernels, the CPU baseline
+with its parity check, and writes the full record to bench_full.json.  --dump-outputs DIR writes what the last timed
+step returned (edge records field by field, inlier masks) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -272,7 +277,7 @@ def _short(v, n=120):
     return v
 
 
-def compact_line(out, full_path=None):
+def compact_line(out, full_path=None, summary=True):
     """The ONE line the driver parses: the contract's keys, `roofline`, `cpu_baseline`, `quality` and the flat
     `summary`, never more than COMPACT_LIMIT bytes; every per-leg block, repetition list and variant lives in bench_full.json.
     Notes are dropped before anything else; if a run ever still overflows, the optional blocks go one by one."""
@@ -288,7 +293,8 @@ def compact_line(out, full_path=None):
         line["cpu_baseline"] = cb
     if isinstance(out.get("exchange"), dict):
         line["exchange"] = {k: v for k, v in out["exchange"].items() if k not in ("note", "uneven_counts")}
-    line["summary"] = out.get("summary") or compact_summary(out)
+    if summary:   # (the flat digest of the --full legs: a plain run has none of them)
+        line["summary"] = out.get("summary") or compact_summary(out)
     if full_path:
         line["full_record"] = full_path
     line = _short(line)
@@ -303,8 +309,12 @@ def compact_line(out, full_path=None):
     return json.dumps(line, separators=(",", ":"))
 
 
-def emit(out):
-    """full record -> bench_full.json beside this script (path on stderr); compact line -> stdout, LAST thing printed"""
+def emit(out, write_full=True):
+    """full record -> bench_full.json beside this script (path on stderr); compact line -> stdout, LAST thing printed.
+    A plain run (write_full=False) has no per-leg blocks to keep: it prints the line and writes nothing."""
+    if not write_full:
+        print(compact_line(out, summary=False), flush=True)
+        return
     full_path = os.environ.get("PGI_BENCH_FULL", os.path.join(ROOT, "bench_full.json"))
     try:
         with open(full_path, "w") as f:
@@ -315,6 +325,40 @@ def emit(out):
         full_path = None
     sys.stderr.flush()
     print(compact_line(out, os.path.basename(full_path) if full_path else None), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_MASK_SAMPLE = 4 << 20      # rows of the inlier mask kept when the whole mask (as f32) would not fit
+DUMP_SAMPLE_SEED = 0xD0
+
+
+def dump_outputs(dirname, edges_host, masks_host, offsets, gathered_host=None):
+    """--dump-outputs: what the timed path returned in its last timed step, as DIR/<name>.npy in f32 / f64 -- every field of the
+    edge records (pgi_edge: one row per pair), the inlier count per pair re-counted from the mask, and the mask itself (all rows
+    when they fit, otherwise a fixed, seeded sample of row indices, which is stored beside it).  N > 1: rank 0's own block plus the
+    essential matrices of every rank's records as gathered."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for name in edges_host.dtype.names:
+        col = edges_host[name]
+        arrays["edges_" + name] = np.ascontiguousarray(col, np.float64)   # (f64 holds every u32 / i32 field exactly)
+    arrays["mask_inliers_per_pair"] = np.add.reduceat(masks_host.astype(np.int64), offsets[:-1]).astype(np.float64) \
+        if len(masks_host) else np.zeros(0)
+    if gathered_host is not None:
+        arrays["gathered_edges_E"] = np.ascontiguousarray(gathered_host["E"], np.float64)
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values()) - 4096 * (len(arrays) + 2)
+    if 4 * len(masks_host) <= room:
+        arrays["masks"] = masks_host.astype(np.float32)
+    else:
+        k = min(DUMP_MASK_SAMPLE, room // 12, len(masks_host))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(masks_host), size=k, replace=False))
+        arrays["masks_sample_rows"] = idx.astype(np.float64)
+        arrays["masks_sample"] = masks_host[idx].astype(np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print("bench.py: %d output arrays (%.1f MB) of the last timed step in %s" % (len(arrays), sum(a.nbytes for a in arrays.values()) / 1e6, dirname),
+          file=sys.stderr)
 
 
 def cpu_model():
@@ -417,13 +461,20 @@ def main():
     ap.add_argument("--inlier-ratio", type=float, default=0.5)
     ap.add_argument("--thr-px", type=float, default=0.75)
     ap.add_argument("--fixed-budget", type=int, default=0, help="0 = adaptive (confidence 0.99, cap 1000)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline time (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary fixed-256 / score_pose lines")
-    ap.add_argument("--no-variants", action="store_true", help="skip the SURVEY 8d variants (ragged, inlier ratios, 0.4 px) and the graph-level runs")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU-baseline time (rank 0, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its parity check")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the secondary fixed-256 / score_pose lines")
+    ap.add_argument("--no-variants", action="store_true", help="--full without the SURVEY 8d variants (ragged, inlier ratios, 0.4 px) and the graph-level runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (quality, replayed profiles, variants, graph-level configs, "
+                         "secondary kernels, CPU baseline and parity) and write bench_full.json; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (edge records field by field, inlier masks) as DIR/<name>.npy")
     ap.add_argument("--require-rccl", action="store_true",
                     help="N > 1: fail (non-zero exit) unless the exchange runs through pgi_allgather_edges over RCCL")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # launched plainly with --gpus N: start the one-process-per-GPU job as a CHILD (never exec after HIP init) and
@@ -533,17 +584,21 @@ def main():
     allgather_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev])) if world > 1 else None
     allgather_uneven_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in ev])) if comm is not None else None
 
-    got = eng.edges_to_numpy(edges)
-    masks_host = masks.cpu().numpy()  # the secondary runs below reuse the device buffers
-    ok = got["status"] == 1
-    errs = np.array([S.rot_err_deg(got["R"][i].reshape(3, 3), b["R"][i]) if ok[i] else np.inf for i in range(P)])
-    auc5 = S.auc_at(errs, 5.0)
+    # what the last timed step returned, on the host: only a run that uses it (--dump-outputs, --full) downloads it
+    got, masks_host = None, None
+    if args.full or (rank == 0 and args.dump_outputs):
+        got = eng.edges_to_numpy(edges)
+        masks_host = masks.cpu().numpy()  # the secondary runs below reuse the device buffers
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, got, masks_host, np.asarray(b["offsets"], np.int64),
+                     eng.edges_to_numpy(gathered) if gathered is not None else None)
 
     value = world * P * args.steps / dt
     bytes_per_launch = P * algorithmic_bytes_per_edge(N)
     achieved_gbs = bytes_per_launch / (kern_ms * 1e-3) / 1e9
     traffic, pmc, roofline_compute, traffic_kernel_us = None, None, None, None
-    tj, prof_name, prof_reason = (None, None, "fixed-budget run") if args.fixed_budget else replay_profile("k1", P, N, L)
+    tj, prof_name, prof_reason = (None, None, "fixed-budget run") if args.fixed_budget else \
+        replay_profile("k1", P, N, L) if args.full else (None, None, "plain run (the profile is replayed with --full)")
     if tj:
         traffic = tj.get("hbm_bytes_per_launch")
         traffic_kernel_us = tj.get("kernel_us_trace_avg")
@@ -572,11 +627,14 @@ def main():
                      "traffic_source": ("replayed from %s; source hash matches the loaded build" % prof_name) if traffic
                                        else "none: %s" % prof_reason,
                      "note": "K1 stages rows once into LDS: VALU / LDS-latency bound by design (SURVEY 8d), see 'valu'"},
-        "quality": {"rot_err_auc_at_5deg": round(auc5, 4), "edges_ok": int(ok.sum()),
-                    "median_rot_err_deg": round(float(np.median(errs)), 4), "mean_hypotheses": float(got["iters"].mean()),
-                    "mean_lo_refits": float(got["lo_runs"].mean())},
         "setup": {"gen_s": round(gen_s, 1)},
     }
+    if args.full:
+        ok = got["status"] == 1
+        errs = np.array([S.rot_err_deg(got["R"][i].reshape(3, 3), b["R"][i]) if ok[i] else np.inf for i in range(P)])
+        out["quality"] = {"rot_err_auc_at_5deg": round(S.auc_at(errs, 5.0), 4), "edges_ok": int(ok.sum()),
+                          "median_rot_err_deg": round(float(np.median(errs)), 4), "mean_hypotheses": float(got["iters"].mean()),
+                          "mean_lo_refits": float(got["lo_runs"].mean())}
     if world > 1:
         out["exchange"] = dict(comm_info or {"rccl_ranks": 0, "transport": "torch.distributed", "rccl_version": 0},
                                allgather_ms=round(allgather_ms, 4),
@@ -593,16 +651,17 @@ def main():
     # 30 flop per Sampson residual and T = the hypotheses actually drawn.  This is ALGORITHMIC work (every model
     # scored on every row); the kernel avoids most of it (pre-verification, exact bail-out), so the figure says how
     # fast the job's nominal arithmetic is retired, not how many flops execute.
-    T_mean = float(got["iters"].mean())
-    f_edge = T_mean * (1.0e4 + 4 * N * 30)
-    tfs = (P / (kern_ms * 1e-3)) * f_edge / 1e12
-    out["valu_algorithmic"] = {"flop_per_edge": round(f_edge), "achieved": round(tfs, 2), "peak": 157.3, "unit": "TFLOP/s",
-                               "frac": round(tfs / 157.3, 4), "hypotheses_per_edge": round(T_mean, 1),
-                               "note": "SURVEY 8d formula; nominal work, not executed flops"}
+    if args.full:
+        T_mean = float(got["iters"].mean())
+        f_edge = T_mean * (1.0e4 + 4 * N * 30)
+        tfs = (P / (kern_ms * 1e-3)) * f_edge / 1e12
+        out["valu_algorithmic"] = {"flop_per_edge": round(f_edge), "achieved": round(tfs, 2), "peak": 157.3, "unit": "TFLOP/s",
+                                   "frac": round(tfs / 157.3, 4), "hypotheses_per_edge": round(T_mean, 1),
+                                   "note": "SURVEY 8d formula; nominal work, not executed flops"}
 
     # (round 6: the variants and the graph-level legs run BEFORE the secondary kernels -- after the matcher leg, which draws the chip's
     #  full power for seconds, the driver children of configs 4 / 5 read 10-20 % slower: 0.099 / 0.112 s against 0.089 / 0.092 s)
-    if rank == 0 and world == 1 and not args.no_variants and not args.fixed_budget:
+    if args.full and rank == 0 and world == 1 and not args.no_variants and not args.fixed_budget:
         # ---- SURVEY 8d's other settings of config 2 (same kernel, same 10 000 pairs; never `value`) -------------------
         def run_variant(batch, thr_v, reps=3, **prm_v):
             if prm_v:
@@ -712,7 +771,7 @@ def main():
                     feat["error"] = r.stderr[-500:]
             out["config3_from_features"] = feat
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         # secondary lines (not `value`): fixed budget of 256 hypotheses; the HBM-bound K2 score kernel
         eng.set_params(fixed_budget=256)
         eng.estimate_pose_batch(db, edges, masks)
@@ -973,7 +1032,7 @@ def main():
                             "round_launches": info_t["rounds"], "query_ms": round(1e3 * t_q, 2),
                             "correspondences_returned": int(qres[2].sum().item())}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # CPU baseline: the build's own CPU restatement (oracle/), NOT OpenCV (absent on this image),
         # same inputs / seeds / mode, all host cores, bounded sample; also re-checks parity on that sample
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -1000,7 +1059,7 @@ def main():
                                "gpu_matches_on_sample": parity, "cpu_model": cpu_model(), "host_logical_cpus": os.cpu_count(),
                                "build": "oracle/pgi_oracle.c: gcc -O3 -mavx2 -mfma -ffp-contract=off, OpenMP over pairs (schedule dynamic)",
                                "opencv": opencv_column(b, m, thr, int(cores))}
-    if world > 1:
+    if world > 1 and (args.full or args.require_rccl):
         # every rank must hold EVERY rank's records after the exchange (checked outside the timed region): the owners
         # publish byte checksums of their blocks through torch.distributed, every rank checks all blocks of its copies
         def checksum(t):
@@ -1023,7 +1082,7 @@ def main():
             if rank == 0:
                 emit(out)
             raise SystemExit("bench.py --require-rccl: a rank holds records that differ from their owner's")
-    if world > 1 and not args.no_variants:
+    if world > 1 and args.full and not args.no_variants:
         # BASELINE configs 4 and 5 on `world` GPUs: rank 0 starts the C++ driver as world child processes (the bench's own
         # ranks idle at the barrier meanwhile: their GPUs are free) and compares every rank's result with the world-1 run
         if rank == 0:
@@ -1036,8 +1095,9 @@ def main():
                     raise
         dist.barrier()
     if rank == 0:
-        out["summary"] = compact_summary(out)
-        emit(out)   # compact line (< 8 KB) LAST on stdout; everything else in bench_full.json
+        if args.full:
+            out["summary"] = compact_summary(out)
+        emit(out, write_full=args.full)   # compact line (< 8 KB) LAST on stdout; with --full everything else in bench_full.json
     if comm is not None:
         comm.close()
     eng.close()
