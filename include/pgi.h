@@ -268,6 +268,47 @@ int pgi_rotation_average_edges(pgi_ctx* ctx, const pgi_edge* d_edges, const uint
                                const pgi_rotavg_params* prm, double* h_R_out, uint32_t* h_iters_out,
                                uint32_t* h_edges_used);
 
+/* ---- translation averaging (global camera positions; not in the reference) ----
+ * Robust Least Unsquared Deviations (Ozyesil & Singer, CVPR 2015) by joint IRLS with an active set; the
+ * specification is tests/transavg_spec.py.  With the global rotations R_k (world->camera)
+ * of pgi_rotation_average and an edge (src = i, dst = j, x_j = R_ij x_i + t_ij), dir = R_j^T t_ij is the world
+ * direction of c_i - c_j; the solver minimises sum_e w_e |c_src - c_dst - s_e dir_e| subject to s_e >= 1.
+ * Gauge and units: the smallest view id of every connected component sits at the origin (exactly 0), and the scale
+ * is set by the constraint s_e >= 1 -- the shortest baselines come out at a length of about 1.  Views without an
+ * edge get position 0.  f64, deterministic (the same input gives the same bits).
+ * Every outer iteration solves a 3V x 3V block Laplacian by block-Jacobi preconditioned CG, stopped at a relative
+ * residual of 1e-4 (environment PGI_TRANSAVG_CG_TOL overrides) or after cg_iters iterations.  Banded, sequence-like
+ * view graphs may run into that cap (the tree and two-level preconditioners of the rotation solve are not wired in
+ * here); PGI_TRANSAVG_TRACE=1 prints the PCG iteration count, the clamped-edge count and the mean step of every outer
+ * iteration to stderr.  No timing or scaling figure exists for this solver yet, and nothing beyond 340 views has
+ * been run. */
+typedef struct {
+    uint32_t src, dst;
+    double dir[3];      /* ~ (c_src - c_dst), world frame; divided by its length unless that is 1 to 1e-12 */
+    double weight;      /* >= 0, e.g. the inlier ratio */
+} pgi_trans_edge;
+typedef struct {
+    uint32_t iters;     /* 60    outer iterations                                   */
+    uint32_t cg_iters;  /* 200   cap of the inner PCG                               */
+    double eps;         /* 1e-3  proximal weight along dir on free edges, in (0, 1] */
+    double delta;       /* 1e-4  floor of the residual in the L1 weight             */
+    double tol;         /* 1e-9  mean step over the views                           */
+} pgi_transavg_params;
+void pgi_default_transavg_params(pgi_transavg_params* p);
+/* h_* host pointers; h_c_out: n_views x 3.  A vertex id >= n_views, src == dst, a zero or non-finite dir or a
+ * negative weight return PGI_ERR_INVALID; zero edges give all-zero positions.  Synchronous. */
+int pgi_translation_average(pgi_ctx* ctx, const pgi_trans_edge* h_edges, uint32_t n_edges, uint32_t n_views,
+                            const pgi_transavg_params* prm, double* h_c_out /* n_views x 3 */, uint32_t* h_iters_out);
+/* The same solve fed from the DEVICE-resident edge table (what pgi_rotation_average_edges takes) and the global
+ * rotations h_R_global (n_views x 9, host): records whose status is not PGI_EDGE_OK are skipped, dir = R_dst^T t
+ * normalised on the device, weight = n_inl / h_rows[p] (h_rows NULL = weight 1).  Only status/n_inl and the
+ * directions of the spanning-forest edges travel to the host.  Bit-identical to pgi_translation_average on the
+ * same directions and weights. */
+int pgi_translation_average_edges(pgi_ctx* ctx, const pgi_edge* d_edges, const uint32_t* h_src, const uint32_t* h_dst,
+                                  const uint32_t* h_rows, uint32_t n_pairs, uint32_t n_views, const double* h_R_global,
+                                  const pgi_transavg_params* prm, double* h_c_out, uint32_t* h_iters_out,
+                                  uint32_t* h_edges_used);
+
 /* ---- multi-GPU: the path's single exchange step -----------------------------------
  * Pairs are sharded over ranks (one process per GPU); every rank estimates its own block and the
  * fixed-size edge records are all-gathered so that each rank holds the full table for the

@@ -722,8 +722,14 @@ size_t PoseGraphBuilder::estimatePoses(const std::vector<ViewPair>& pairs, PoseG
 PoseGraphBuilder::GlobalRotations PoseGraphBuilder::estimateAndAverage(const std::vector<ViewPair>& pairs, PoseGraph& poseGraph_,
                                                                         size_t numViews, uint64_t seed,
                                                                         std::vector<pgi_edge>* edges_out,
-                                                                        const pgi_rotavg_params* rotavgParams) {
+                                                                        const pgi_rotavg_params* rotavgParams,
+                                                                        GlobalPositions* positions_out,
+                                                                        const pgi_transavg_params* transavgParams) {
     GlobalRotations out;
+    if (positions_out) {
+        *positions_out = GlobalPositions{};
+        positions_out->positions.assign(numViews, Vector3d{{0, 0, 0}});
+    }
     out.rotations.assign(numViews, Matrix3d{{1, 0, 0, 0, 1, 0, 0, 0, 1}});
     const size_t P = pairs.size();
     if (!P || !numViews) return out;
@@ -762,6 +768,11 @@ PoseGraphBuilder::GlobalRotations PoseGraphBuilder::estimateAndAverage(const std
                                              (uint32_t)numViews, rotavgParams, out.rotations[0].data(), &out.iterations,
                                              &out.edgesUsed));
     statistics.addTime("[Rotation averaging]", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_avg).count(), 1);
+    if (positions_out) {
+        const std::chrono::steady_clock::time_point t_trn = std::chrono::steady_clock::now();
+        *positions_out = averageTranslations(table.as<pgi_edge>(), src, dst, &rows, numViews, out, transavgParams);
+        statistics.addTime("[Translation averaging]", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_trn).count(), 1);
+    }
     if (inserter.joinable()) inserter.join();
     statistics.addTime("[Pose estimation] pose graph insertion (beside the averaging)", insertSeconds, 1);
     return out;
@@ -791,6 +802,50 @@ PoseGraphBuilder::GlobalRotations PoseGraphBuilder::averageRotations(const PoseG
     out.edgesUsed = (uint32_t)re.size();
     Engine::check(pgi_rotation_average(engine->get(), re.data(), (uint32_t)re.size(), (uint32_t)numViews, rotavgParams,
                                        out.rotations[0].data(), &out.iterations));
+    return out;
+}
+
+PoseGraphBuilder::GlobalPositions PoseGraphBuilder::averageTranslations(const PoseGraph& poseGraph_, size_t numViews,
+                                                                         const GlobalRotations& rotations_,
+                                                                         const pgi_transavg_params* transavgParams) {
+    GlobalPositions out;
+    out.positions.assign(numViews, Vector3d{{0, 0, 0}});
+    if (!numViews) return out;
+    if (rotations_.rotations.size() != numViews) throw std::invalid_argument("averageTranslations: one global rotation per view is needed");
+    std::vector<pgi_trans_edge> te(poseGraph_.numEdges());
+    poseGraph_.forEachEdge(0, te.size(), [&](size_t k, const PoseGraphEdge& e) {
+        pgi_trans_edge r{};
+        r.src = (uint32_t)e.getSourceId();
+        r.dst = (uint32_t)e.getDestinationId();
+        const Vector3d& t = e.getValue().getTranslation();
+        if (r.dst < numViews) {  // (an id out of range is reported by the library)
+            const Matrix3d& R = rotations_.rotations[r.dst];
+            for (int c = 0; c < 3; ++c) r.dir[c] = R[c] * t[0] + R[3 + c] * t[1] + R[6 + c] * t[2];  // R_dst^T t
+        }
+        r.weight = e.getScore();
+        te[k] = r;
+    });
+    out.edgesUsed = (uint32_t)te.size();
+    static_assert(sizeof(Vector3d) == 24, "Vector3d must be 3 packed doubles");
+    Engine::check(pgi_translation_average(engine->get(), te.data(), (uint32_t)te.size(), (uint32_t)numViews, transavgParams,
+                                          out.positions[0].data(), &out.iterations));
+    return out;
+}
+
+PoseGraphBuilder::GlobalPositions PoseGraphBuilder::averageTranslations(const pgi_edge* d_edges, const std::vector<uint32_t>& src,
+                                                                         const std::vector<uint32_t>& dst,
+                                                                         const std::vector<uint32_t>* rows, size_t numViews,
+                                                                         const GlobalRotations& rotations_,
+                                                                         const pgi_transavg_params* transavgParams) {
+    GlobalPositions out;
+    out.positions.assign(numViews, Vector3d{{0, 0, 0}});
+    if (!numViews) return out;
+    if (rotations_.rotations.size() != numViews || src.size() != dst.size() || (rows && rows->size() != src.size()))
+        throw std::invalid_argument("averageTranslations: inconsistent table sizes");
+    static_assert(sizeof(Vector3d) == 24, "Vector3d must be 3 packed doubles");
+    Engine::check(pgi_translation_average_edges(engine->get(), d_edges, src.data(), dst.data(), rows ? rows->data() : nullptr,
+                                                (uint32_t)src.size(), (uint32_t)numViews, rotations_.rotations[0].data(), transavgParams,
+                                                out.positions[0].data(), &out.iterations, &out.edgesUsed));
     return out;
 }
 

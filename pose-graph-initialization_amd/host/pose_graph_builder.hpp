@@ -778,12 +778,30 @@ class PoseGraphBuilder {  // include/pose_graph_builder.h:25-171
         std::vector<Matrix3d> rotations;
         uint32_t iterations = 0, edgesUsed = 0;
     };
+    // Global camera centres c_k (world frame) from translation averaging (include/pgi.h: pgi_translation_average): the
+    // smallest view of every connected component sits at the origin, the shortest baselines have a length of about 1.
+    struct GlobalPositions {
+        std::vector<Vector3d> positions;
+        uint32_t iterations = 0, edgesUsed = 0;
+    };
+    // positions_out (optional): the translation averaging runs on the same gathered device table right after the rotation
+    // averaging, with its rotations -- replicated on every rank exactly as the rotation solve is.
     GlobalRotations estimateAndAverage(const std::vector<ViewPair>& pairs, PoseGraph& poseGraph_, size_t numViews,
                                        uint64_t seed = 0, std::vector<pgi_edge>* edges_out = nullptr,
-                                       const pgi_rotavg_params* rotavgParams = nullptr);
+                                       const pgi_rotavg_params* rotavgParams = nullptr, GlobalPositions* positions_out = nullptr,
+                                       const pgi_transavg_params* transavgParams = nullptr);
     // Rotation averaging over the edges already in a pose graph (weights = edge scores), e.g. after run().
     GlobalRotations averageRotations(const PoseGraph& poseGraph_, size_t numViews,
                                      const pgi_rotavg_params* rotavgParams = nullptr);
+    // Translation averaging over the edges already in a pose graph (direction = R_dst^T t of every edge with the given
+    // global rotations, weights = edge scores), e.g. after run() and averageRotations().
+    GlobalPositions averageTranslations(const PoseGraph& poseGraph_, size_t numViews, const GlobalRotations& rotations_,
+                                        const pgi_transavg_params* transavgParams = nullptr);
+    // The same from a device-resident edge table (what pgi_rotation_average_edges takes): pair p = (src[p], dst[p]) with
+    // record d_edges[p], weight = n_inl / rows[p] (rows null: weight 1).
+    GlobalPositions averageTranslations(const pgi_edge* d_edges, const std::vector<uint32_t>& src, const std::vector<uint32_t>& dst,
+                                        const std::vector<uint32_t>* rows, size_t numViews, const GlobalRotations& rotations_,
+                                        const pgi_transavg_params* transavgParams = nullptr);
 
     struct RunStatistics {  // the reference's RunningStatistics keys that concern this path (utils.h:15-73)
         size_t pairsProcessed = 0, edgesAdded = 0, pathsSearched = 0, pathsFound = 0, touchedNodes = 0,

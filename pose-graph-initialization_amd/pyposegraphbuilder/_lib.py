@@ -40,12 +40,23 @@ class RotAvgParams(C.Structure):
                 ("sigma_deg", C.c_double), ("tol", C.c_double)]
 
 
+class TransEdge(C.Structure):
+    _fields_ = [("src", C.c_uint32), ("dst", C.c_uint32), ("dir", C.c_double * 3), ("weight", C.c_double)]
+
+
+class TransAvgParams(C.Structure):
+    _fields_ = [("iters", C.c_uint32), ("cg_iters", C.c_uint32), ("eps", C.c_double), ("delta", C.c_double),
+                ("tol", C.c_double)]
+
+
 EDGE_DTYPE = np.dtype([("E", "f8", 9), ("R", "f8", 9), ("t", "f8", 3), ("status", "i4"),
                        ("n_inl", "u4"), ("score", "u4"), ("iters", "u4"), ("votes", "u4"),
                        ("cand", "u4"), ("used_guess", "u4"), ("lo_runs", "u4")])
 ROT_EDGE_DTYPE = np.dtype([("src", "u4"), ("dst", "u4"), ("R", "f8", 9), ("weight", "f8")])
 assert EDGE_DTYPE.itemsize == C.sizeof(Edge) == 200
+TRANS_EDGE_DTYPE = np.dtype([("src", "u4"), ("dst", "u4"), ("dir", "f8", 3), ("weight", "f8")])
 assert ROT_EDGE_DTYPE.itemsize == C.sizeof(RotEdge)
+assert TRANS_EDGE_DTYPE.itemsize == C.sizeof(TransEdge) == 40
 
 # every symbol include/pgi.h declares
 SYMBOLS = ["pgi_last_error", "pgi_device_count", "pgi_default_params", "pgi_create", "pgi_destroy",
@@ -56,7 +67,8 @@ SYMBOLS = ["pgi_last_error", "pgi_device_count", "pgi_default_params", "pgi_crea
            "pgi_get_params", "pgi_rotation_average_edges", "pgi_comm_unique_id", "pgi_comm_init_rccl", "pgi_comm_init_host",
            "pgi_comm_destroy", "pgi_comm_info", "pgi_comm_rccl_probe", "pgi_allgather_edges", "pgi_allgatherv", "pgi_host_register", "pgi_host_unregister",
            "pgi_tracklets_create", "pgi_tracklets_destroy", "pgi_tracklets_add_batch", "pgi_tracklets_get_batch",
-           "pgi_tracklets_info", "pgi_tracklets_track"]
+           "pgi_tracklets_info", "pgi_tracklets_track",
+           "pgi_default_transavg_params", "pgi_translation_average", "pgi_translation_average_edges"]
 COMM_ID_BYTES = 128
 # pgi_allgatherv_fn: int (*)(void* user, const void* send, uint64 send_bytes, void* recv, const uint64* recv_bytes, uint32 world)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32)
@@ -162,6 +174,11 @@ def load():
     lib.pgi_rotation_average.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                          C.POINTER(RotAvgParams), C.c_void_p, C.c_void_p]
     lib.pgi_default_rotavg_params.argtypes = [C.POINTER(RotAvgParams)]
+    lib.pgi_default_transavg_params.argtypes = [C.POINTER(TransAvgParams)]
+    lib.pgi_translation_average.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                            C.POINTER(TransAvgParams), C.c_void_p, C.c_void_p]
+    lib.pgi_translation_average_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.POINTER(TransAvgParams), C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

@@ -149,3 +149,17 @@ def edges_to_rotation_graph(edges_np, src, dst, rows=None):
     else:
         w = edges_np["n_inl"][ok].astype(np.float64) / np.maximum(np.asarray(rows, np.float64)[ok], 1.0)
     return np.asarray(src)[ok], np.asarray(dst)[ok], edges_np["R"][ok].reshape(-1, 3, 3), w
+
+
+def edges_to_translation_graph(edges_np, src, dst, R_global, rows=None):
+    """Edge records of the OK edges plus the global rotations (world->camera, [V, 3, 3]) -> (src, dst, gamma, weight)
+    for translation_average: gamma = R_dst^T t normalised, the world direction of c_src - c_dst, in the operation
+    order of the device kernel (so Engine.translation_average on it equals translation_average_edges bit for bit);
+    weights as in edges_to_rotation_graph."""
+    s, d, _, w = edges_to_rotation_graph(edges_np, src, dst, rows)
+    ok = edges_np["status"] == 1
+    R = np.asarray(R_global, np.float64).reshape(-1, 3, 3)[np.asarray(d, np.int64)]
+    t = edges_np["t"][ok].reshape(-1, 3)
+    g = np.stack([R[:, 0, i] * t[:, 0] + R[:, 1, i] * t[:, 1] + R[:, 2, i] * t[:, 2] for i in range(3)], 1)
+    n = np.sqrt(g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1] + g[:, 2] * g[:, 2])
+    return s, d, g / n[:, None], w

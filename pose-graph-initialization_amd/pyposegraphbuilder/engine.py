@@ -254,6 +254,53 @@ class Engine:
             C.byref(iters), C.byref(used)))
         return R, iters.value, used.value
 
+    # ---- translation averaging --------------------------------------------------------------------
+    def _transavg_params(self, kw):
+        prm = L.TransAvgParams()
+        self._lib.pgi_default_transavg_params(C.byref(prm))
+        for k, v in kw.items():
+            if not hasattr(prm, k):
+                raise TypeError("unknown parameter %r" % k)
+            setattr(prm, k, v)
+        return prm
+
+    def translation_average(self, src, dst, directions, weight, n_views, **kw):
+        """Robust LUD translation averaging over edges (src, dst, unit world direction of c_src - c_dst, weight)
+        -> (c[n_views,3], iters).  The smallest view of every component sits at 0; the shortest baselines are ~1."""
+        E = len(src)
+        edges = np.zeros(E, L.TRANS_EDGE_DTYPE)
+        edges["src"], edges["dst"] = src, dst
+        edges["dir"] = np.asarray(directions, np.float64).reshape(E, 3)
+        edges["weight"] = weight
+        prm = self._transavg_params(kw)
+        c = np.zeros((n_views, 3))
+        iters = C.c_uint32(0)
+        self._bind_stream()
+        L.check(self._lib.pgi_translation_average(self._ctx, edges.ctypes.data_as(C.c_void_p), E, n_views, C.byref(prm),
+                                                  c.ctypes.data_as(C.c_void_p), C.byref(iters)))
+        return c, iters.value
+
+    def translation_average_edges(self, edges, src, dst, rows, n_views, R_global, **kw):
+        """The same solve fed from the device-resident edge table (uint8 [P, 200]) and the global rotations
+        (world->camera, [n_views, 3, 3], e.g. from rotation_average_edges): direction = R_dst^T t of every OK record,
+        weight = n_inl / rows.  -> (c[n_views,3], iters, edges_used)"""
+        P = int(edges.shape[0])
+        src = np.ascontiguousarray(src, np.uint32)
+        dst = np.ascontiguousarray(dst, np.uint32)
+        rows = None if rows is None else np.ascontiguousarray(rows, np.uint32)
+        Rg = np.ascontiguousarray(R_global, np.float64).reshape(-1)
+        if Rg.size != 9 * n_views:
+            raise ValueError("R_global must hold n_views 3 x 3 matrices")
+        prm = self._transavg_params(kw)
+        c = np.zeros((n_views, 3))
+        iters, used = C.c_uint32(0), C.c_uint32(0)
+        self._bind_stream()
+        L.check(self._lib.pgi_translation_average_edges(
+            self._ctx, _ptr(edges), src.ctypes.data_as(C.c_void_p), dst.ctypes.data_as(C.c_void_p),
+            None if rows is None else rows.ctypes.data_as(C.c_void_p), P, n_views, Rg.ctypes.data_as(C.c_void_p), C.byref(prm),
+            c.ctypes.data_as(C.c_void_p), C.byref(iters), C.byref(used)))
+        return c, iters.value, used.value
+
     # ---- multi-GPU exchange (include/pgi.h: pgi_comm_*, pgi_allgather_edges) ----------------------------------------
     def comm_info(self):
         w, r, k = C.c_uint32(1), C.c_uint32(0), C.c_uint32(0)
