@@ -478,6 +478,51 @@ int pgi_tracklets_info(const pgi_tracklets* trk, uint64_t* n_tracks, uint64_t* n
 int pgi_tracklets_track(pgi_tracklets* trk, uint64_t index, uint64_t* h_members, uint32_t capacity,
                         uint32_t* n_members);
 
+/* ---- triangulation of multi-view tracks (sparse 3-D points from the global poses; not in the reference) ----
+ * One track per lane: the N-view midpoint, Gauss-Newton steps on the pixel reprojection error, greedy drop-the-worst
+ * trimming and a parallax test.  The specification is tests/triangulate_spec.py; the
+ * outputs equal it bit for bit, do not depend on the launch shape or on the other tracks, and the same input gives the
+ * same bits.  f64 throughout. */
+#define PGI_TRI_OK 0            /* X written                                                         */
+#define PGI_TRI_TOO_FEW 1       /* fewer than min_views eligible observations                        */
+#define PGI_TRI_DEGENERATE 2    /* the midpoint system is singular (parallel rays)                   */
+#define PGI_TRI_BEHIND 3        /* error above thr_px and a used depth is not positive               */
+#define PGI_TRI_REPROJ 4        /* error above thr_px after trimming                                 */
+#define PGI_TRI_LOW_PARALLAX 5  /* X written; the largest angle between two used rays is too small   */
+#define PGI_TRI_STATUS_COUNT 6
+typedef struct {
+    uint32_t min_views;     /* 2     eligible observations a track needs (never below 2)            */
+    uint32_t refine_iters;  /* 3     Gauss-Newton steps after the midpoint                          */
+    uint32_t max_drops;     /* 2     observations trimming may drop per track                       */
+    uint32_t reserved;
+    double thr_px;          /* 2.0   reprojection error, pixels                                     */
+    double min_angle_deg;   /* 1.5   parallax below this gives PGI_TRI_LOW_PARALLAX                 */
+} pgi_triangulate_params;
+void pgi_default_triangulate_params(pgi_triangulate_params* p);
+/* Track t owns d_members[d_track_begin[t] .. d_track_begin[t + 1]), each (view << 32 | keypoint) -- the store's member
+ * format, in member order; an empty run gives PGI_TRI_TOO_FEW.  h_views[v]: the keypoints (device pointer) and
+ * intrinsics of view v; h_R: n_views x 9 world->camera (pgi_rotation_average); h_c: n_views x 3 centres
+ * (pgi_translation_average); h_has_pose: n_views bytes or NULL = every view has a pose.  An observation counts when its
+ * view is < n_views and has a pose, its keypoint is < n of the view, its pixel is finite and no earlier counted
+ * observation of the track has the same view.
+ * Outputs (device): d_X n_tracks x 3 (NaN unless OK / LOW_PARALLAX), d_status n_tracks bytes; optional (may be NULL):
+ * d_err n_tracks (RMS reprojection error over the used observations), d_n_used n_tracks, d_obs_state one byte per member
+ * (0 not counted, 1 used, 2 dropped as an outlier).  h_status_counts (host, optional): PGI_TRI_STATUS_COUNT counters.
+ * Asynchronous on the context's stream when h_status_counts and d_obs_state are handled as follows: with
+ * h_status_counts the call waits for the kernel; without d_obs_state the call reads d_track_begin[n_tracks] first (the
+ * size of its own scratch).  n_tracks = 0 succeeds.  PGI_ERR_INVALID: a NULL argument, non-finite R / c / cx / cy or
+ * non-positive fx / fy of a view that has a pose, min_views < 2, thr_px <= 0. */
+int pgi_triangulate_tracks(pgi_ctx* ctx, const uint32_t* d_track_begin, const uint64_t* d_members, uint32_t n_tracks,
+                           const pgi_keypoint_view* h_views, const double* h_R, const double* h_c, const uint8_t* h_has_pose,
+                           uint32_t n_views, const pgi_triangulate_params* prm, double* d_X, double* d_err, uint32_t* d_n_used,
+                           uint8_t* d_status, uint8_t* d_obs_state, uint32_t* h_status_counts);
+/* The same kernel on the store's current by-track ordering (track indices and member order of pgi_tracklets_track); no
+ * member leaves the device.  Outputs are sized by pgi_tracklets_info: n_tracks tracks, n_events members. */
+int pgi_tracklets_triangulate(pgi_tracklets* trk, const pgi_keypoint_view* h_views, const double* h_R, const double* h_c,
+                              const uint8_t* h_has_pose, uint32_t n_views, const pgi_triangulate_params* prm, double* d_X,
+                              double* d_err, uint32_t* d_n_used, uint8_t* d_status, uint8_t* d_obs_state,
+                              uint32_t* h_status_counts);
+
 #ifdef __cplusplus
 }
 #endif

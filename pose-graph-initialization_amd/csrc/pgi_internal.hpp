@@ -90,4 +90,18 @@ struct pgi_ctx {
     int class_overlap = 1;  // env PGI_CLASS_OVERLAP=0: one class after the other on the caller's stream
     int k1_nw = 0;          // wavefronts per pair of K1: 0 = by batch size (launch_estimate), 1 / 2 / 4 forced (env PGI_K1_NW)
     int k1_persistent = 1;  // size-class launches as persistent grids (resident workgroups pull pairs); env PGI_K1_PERSISTENT=0: grid = pairs
+    // track triangulation (pgi_triangulate.hip): grow-only device scratch (view table, length order, member states) and the
+    // page-locked mirror of the view table with the event of its last upload
+    void* d_tri_ws = nullptr;
+    size_t tri_ws_bytes = 0;
+    void* h_tri_stage = nullptr;
+    size_t tri_stage_bytes = 0;
+    hipEvent_t tri_stage_ev = nullptr;
 };
+
+struct pgi_tracklets;
+namespace pgi {
+// the store's current by-track ordering (pgi_tracklets.hip): offsets (n_tracks + 1), members, counts
+void tracklets_by_track(const pgi_tracklets* t, pgi_ctx** ctx, const uint32_t** d_track_begin, const uint64_t** d_members,
+                        uint32_t* n_tracks, uint64_t* n_members);
+}  // namespace pgi

@@ -110,6 +110,15 @@ struct pgi_tracklets {
     uint32_t last_rounds = 0;
 };
 
+void pgi::tracklets_by_track(const pgi_tracklets* t, pgi_ctx** ctx, const uint32_t** d_track_begin, const uint64_t** d_members,
+                             uint32_t* n_tracks, uint64_t* n_members) {
+    *ctx = t->ctx;
+    *d_track_begin = t->trk_begin.as<uint32_t>();
+    *d_members = t->mem_key[t->cur].as<uint64_t>();
+    *n_tracks = t->n_tracks;
+    *n_members = t->n_events;
+}
+
 namespace {
 
 struct PairDesc {

@@ -1778,6 +1778,82 @@ PoseGraphBuilder::FeatureRunStatistics PoseGraphBuilder::processFeatures(const s
     return st;
 }
 
+PoseGraphBuilder::TriangulatedPoints PoseGraphBuilder::triangulateTracks(const std::vector<uint32_t>& trackBegin,
+                                                                         const std::vector<uint64_t>& members,
+                                                                         const std::vector<ViewFeaturesRef>& views,
+                                                                         const GlobalRotations& rotations_,
+                                                                         const GlobalPositions& positions_,
+                                                                         const std::vector<uint8_t>* hasPose,
+                                                                         const pgi_triangulate_params* params) {
+    TriangulatedPoints out;
+    const size_t V = views.size(), T = trackBegin.empty() ? 0 : trackBegin.size() - 1;
+    if (rotations_.rotations.size() != V || positions_.positions.size() != V)
+        throw std::invalid_argument("triangulateTracks: one global rotation and one position per view are needed");
+    if (hasPose && hasPose->size() != V) throw std::invalid_argument("triangulateTracks: one pose flag per view is needed");
+    if (T && trackBegin.back() != members.size()) throw std::invalid_argument("triangulateTracks: the last offset must be the member count");
+    if (!T) return out;
+    pgi_ctx* ctx = engine->get();
+    HIP_OK(hipSetDevice(engineDevice(ctx)));
+    struct Block {  // one device block: keypoints, offsets, members, outputs
+        void* p = nullptr;
+        ~Block() { if (p) (void)hipFree(p); }
+    } block;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t M = members.size();
+    std::vector<size_t> kpOff(V + 1, 0);
+    for (size_t v = 0; v < V; ++v) kpOff[v + 1] = kpOff[v] + up(views[v].size() * 8);
+    const size_t oBegin = kpOff[V], oMem = oBegin + up((T + 1) * 4), oX = oMem + up(M * 8), oErr = oX + up(T * 24), oUsed = oErr + up(T * 8),
+                 oStatus = oUsed + up(T * 4), oState = oStatus + up(T), total = oState + up(M);
+    HIP_OK(hipMalloc(&block.p, total));
+    char* d = (char*)block.p;
+    hipStream_t s = engineStream(ctx);
+    std::vector<pgi_keypoint_view> kv(V);
+    std::vector<double> R(V * 9), c(V * 3);
+    for (size_t v = 0; v < V; ++v) {
+        const size_t n = views[v].size();
+        if (n) {
+            if (!views[v].keypoints) throw PgiError("triangulateTracks: null keypoint array");
+            HIP_OK(hipMemcpyAsync(d + kpOff[v], views[v].keypoints, n * 8, hipMemcpyHostToDevice, s));
+        }
+        kv[v] = pgi_keypoint_view{n ? (const float*)(d + kpOff[v]) : nullptr, (uint32_t)n, 0, views[v].focalLength, views[v].focalLength,
+                                  views[v].width / 2.0, views[v].height / 2.0};  // K = [f 0 w/2; 0 f h/2] (pose_graph_builder.h:286)
+        std::memcpy(&R[v * 9], rotations_.rotations[v].data(), 72);
+        std::memcpy(&c[v * 3], positions_.positions[v].data(), 24);
+    }
+    HIP_OK(hipMemcpyAsync(d + oBegin, trackBegin.data(), (T + 1) * 4, hipMemcpyHostToDevice, s));
+    if (M) HIP_OK(hipMemcpyAsync(d + oMem, members.data(), M * 8, hipMemcpyHostToDevice, s));
+    Engine::check(pgi_triangulate_tracks(ctx, (const uint32_t*)(d + oBegin), (const uint64_t*)(d + oMem), (uint32_t)T, kv.data(), R.data(),
+                                         c.data(), hasPose ? hasPose->data() : nullptr, (uint32_t)V, params, (double*)(d + oX),
+                                         (double*)(d + oErr), (uint32_t*)(d + oUsed), (uint8_t*)(d + oStatus), (uint8_t*)(d + oState),
+                                         out.counts.data()));
+    out.points.resize(T);
+    out.status.resize(T);
+    out.rmsError.resize(T);
+    out.viewsUsed.resize(T);
+    out.observationState.resize(M);
+    HIP_OK(hipMemcpyAsync(out.points.data(), d + oX, T * 24, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(out.status.data(), d + oStatus, T, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(out.rmsError.data(), d + oErr, T * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(out.viewsUsed.data(), d + oUsed, T * 4, hipMemcpyDeviceToHost, s));
+    if (M) HIP_OK(hipMemcpyAsync(out.observationState.data(), d + oState, M, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return out;
+}
+
+PoseGraphBuilder::TriangulatedPoints PoseGraphBuilder::triangulateTracks(const Tracklets& tracks_, const std::vector<ViewFeaturesRef>& views,
+                                                                         const GlobalRotations& rotations_,
+                                                                         const GlobalPositions& positions_,
+                                                                         const std::vector<uint8_t>* hasPose,
+                                                                         const pgi_triangulate_params* params) {
+    std::vector<uint32_t> begin(1, 0);
+    std::vector<uint64_t> members;
+    for (size_t t = 0; t < tracks_.trackNumber(); ++t) {
+        for (const Tracklets::Pair& m : tracks_.track(t)) members.push_back(((uint64_t)m.first << 32) | (uint64_t)(uint32_t)m.second);
+        begin.push_back((uint32_t)members.size());
+    }
+    return triangulateTracks(begin, members, views, rotations_, positions_, hasPose, params);
+}
+
 namespace pose {
 // pose_utils.h:172-252 -- one re-entrant call on host pointers (pgi_pose_from_essential_host: private slot of the context,
 // no allocation once warm); every row votes, as in the reference (:203)

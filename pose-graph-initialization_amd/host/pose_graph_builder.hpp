@@ -803,6 +803,29 @@ class PoseGraphBuilder {  // include/pose_graph_builder.h:25-171
                                         const std::vector<uint32_t>* rows, size_t numViews, const GlobalRotations& rotations_,
                                         const pgi_transavg_params* transavgParams = nullptr);
 
+    // Sparse 3-D points of multi-view tracks from the global poses (include/pgi.h: pgi_triangulate_tracks; specification
+    // tests/triangulate_spec.py): N-view midpoint, Gauss-Newton on the reprojection error, greedy trimming, parallax test.
+    struct TriangulatedPoints {
+        std::vector<Vector3d> points;        // NaN unless the status is PGI_TRI_OK or PGI_TRI_LOW_PARALLAX
+        std::vector<uint8_t> status;         // PGI_TRI_*
+        std::vector<double> rmsError;        // pixels, over the used observations
+        std::vector<uint32_t> viewsUsed;
+        std::vector<uint8_t> observationState;  // per member: 0 not counted, 1 used, 2 dropped as an outlier
+        std::array<uint32_t, PGI_TRI_STATUS_COUNT> counts{};
+    };
+    struct ViewFeaturesRef;
+    // trackBegin (tracks + 1 offsets) and members (view << 32 | keypoint) in host memory; views: keypoints and pinhole
+    // camera of every view (descriptors are not read); one rotation and one centre per view; hasPose null = every view.
+    // Tracks, keypoints and outputs make one round trip; the kernel is the one the device store uses.
+    TriangulatedPoints triangulateTracks(const std::vector<uint32_t>& trackBegin, const std::vector<uint64_t>& members,
+                                         const std::vector<ViewFeaturesRef>& views, const GlobalRotations& rotations_,
+                                         const GlobalPositions& positions_, const std::vector<uint8_t>* hasPose = nullptr,
+                                         const pgi_triangulate_params* params = nullptr);
+    // The same for a host-only store (host/tracklets.hpp): uploaded as trackBegin and members first, in track order.
+    TriangulatedPoints triangulateTracks(const class Tracklets& tracks_, const std::vector<ViewFeaturesRef>& views,
+                                         const GlobalRotations& rotations_, const GlobalPositions& positions_,
+                                         const std::vector<uint8_t>* hasPose = nullptr, const pgi_triangulate_params* params = nullptr);
+
     struct RunStatistics {  // the reference's RunningStatistics keys that concern this path (utils.h:15-73)
         size_t pairsProcessed = 0, edgesAdded = 0, pathsSearched = 0, pathsFound = 0, touchedNodes = 0,
                posesFromGuess = 0, hypotheses = 0, waves = 0;

@@ -5,12 +5,14 @@ All compute runs in libpgi.so (HIP, gfx950); there is no CPU fallback.
 """
 from . import synthetic  # noqa: F401
 from ._lib import EDGE_DTYPE, PgiError, default_params  # noqa: F401
+from ._lib import (TRI_BEHIND, TRI_DEGENERATE, TRI_LOW_PARALLAX, TRI_OK, TRI_REPROJ, TRI_STATUS_COUNT,  # noqa: F401
+                   TRI_STATUS_NAMES, TRI_TOO_FEW)
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily
-    if name in ("Engine",):
-        from .engine import Engine
-        return Engine
+    if name in ("Engine", "DeviceTracklets", "Triangulation"):
+        from . import engine
+        return getattr(engine, name)
     if name in ("PoseGraphBuilder", "findEssentialMatrix", "bindProcessToDeviceNode"):
         from . import builder
         return getattr(builder, name)

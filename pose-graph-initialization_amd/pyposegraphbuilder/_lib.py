@@ -49,6 +49,17 @@ class TransAvgParams(C.Structure):
                 ("tol", C.c_double)]
 
 
+class TriangulateParams(C.Structure):
+    """pgi_triangulate_params (include/pgi.h)."""
+    _fields_ = [("min_views", C.c_uint32), ("refine_iters", C.c_uint32), ("max_drops", C.c_uint32), ("reserved", C.c_uint32),
+                ("thr_px", C.c_double), ("min_angle_deg", C.c_double)]
+
+
+# per-track status of the triangulation (PGI_TRI_* of include/pgi.h)
+TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_BEHIND, TRI_REPROJ, TRI_LOW_PARALLAX = range(6)
+TRI_STATUS_COUNT = 6
+TRI_STATUS_NAMES = ("OK", "TOO_FEW", "DEGENERATE", "BEHIND", "REPROJ", "LOW_PARALLAX")
+
 EDGE_DTYPE = np.dtype([("E", "f8", 9), ("R", "f8", 9), ("t", "f8", 3), ("status", "i4"),
                        ("n_inl", "u4"), ("score", "u4"), ("iters", "u4"), ("votes", "u4"),
                        ("cand", "u4"), ("used_guess", "u4"), ("lo_runs", "u4")])
@@ -68,7 +79,8 @@ SYMBOLS = ["pgi_last_error", "pgi_device_count", "pgi_default_params", "pgi_crea
            "pgi_comm_destroy", "pgi_comm_info", "pgi_comm_rccl_probe", "pgi_allgather_edges", "pgi_allgatherv", "pgi_host_register", "pgi_host_unregister",
            "pgi_tracklets_create", "pgi_tracklets_destroy", "pgi_tracklets_add_batch", "pgi_tracklets_get_batch",
            "pgi_tracklets_info", "pgi_tracklets_track",
-           "pgi_default_transavg_params", "pgi_translation_average", "pgi_translation_average_edges"]
+           "pgi_default_transavg_params", "pgi_translation_average", "pgi_translation_average_edges",
+           "pgi_default_triangulate_params", "pgi_triangulate_tracks", "pgi_tracklets_triangulate"]
 COMM_ID_BYTES = 128
 # pgi_allgatherv_fn: int (*)(void* user, const void* send, uint64 send_bytes, void* recv, const uint64* recv_bytes, uint32 world)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32)
@@ -179,6 +191,11 @@ def load():
                                             C.POINTER(TransAvgParams), C.c_void_p, C.c_void_p]
     lib.pgi_translation_average_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                   C.c_void_p, C.POINTER(TransAvgParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pgi_default_triangulate_params.restype = None
+    lib.pgi_default_triangulate_params.argtypes = [C.POINTER(TriangulateParams)]
+    view_args = [C.POINTER(KeypointView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(TriangulateParams)]
+    lib.pgi_triangulate_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + view_args + [C.c_void_p] * 6
+    lib.pgi_tracklets_triangulate.argtypes = [C.c_void_p] + view_args + [C.c_void_p] * 6
     _lib = lib
     return lib
 

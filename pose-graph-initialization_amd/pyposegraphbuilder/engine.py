@@ -14,6 +14,23 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+class Triangulation:
+    """Result of Engine.triangulate_tracks / DeviceTracklets.triangulate: device tensors X [T,3] f64 (NaN unless the
+    status is TRI_OK or TRI_LOW_PARALLAX), status [T] u8 (pyposegraphbuilder.TRI_*), err_rms [T] f64, n_used [T] i32,
+    obs_state [members] u8 (0 not counted, 1 used, 2 dropped as an outlier; the optional three are None when not asked
+    for) and counts, a numpy array with the number of tracks per status."""
+
+    def __init__(self, X, status, err_rms, n_used, obs_state, counts):
+        self.X, self.status, self.err_rms, self.n_used, self.obs_state, self.counts = X, status, err_rms, n_used, obs_state, counts
+
+    def numpy(self):
+        """-> dict of numpy arrays (n_used as uint32)."""
+        f = lambda t: None if t is None else t.cpu().numpy()
+        n = f(self.n_used)
+        return dict(X=f(self.X), status=f(self.status), err_rms=f(self.err_rms), n_used=None if n is None else n.astype(np.uint32),
+                    obs_state=f(self.obs_state), counts=self.counts.copy())
+
+
 class Engine:
     def __init__(self, device=None, **params):
         lib = L.load()
@@ -301,6 +318,66 @@ class Engine:
             c.ctypes.data_as(C.c_void_p), C.byref(iters), C.byref(used)))
         return c, iters.value, used.value
 
+    # ---- triangulation of tracks ------------------------------------------------------------------
+    def _triangulate_args(self, keypoints, R, c, has_pose, kw):
+        """-> (view array, R, c, has_pose, n_views, params): the host arguments pgi_triangulate_tracks and
+        pgi_tracklets_triangulate share."""
+        prm = L.TriangulateParams()
+        self._lib.pgi_default_triangulate_params(C.byref(prm))
+        for k, v in kw.items():
+            if not hasattr(prm, k) or k == "reserved":
+                raise TypeError("unknown parameter %r" % k)
+            setattr(prm, k, v)
+        V = len(keypoints)
+        Rh = np.ascontiguousarray(R, np.float64).reshape(-1)
+        ch = np.ascontiguousarray(c, np.float64).reshape(-1)
+        if Rh.size != 9 * V or ch.size != 3 * V:
+            raise ValueError("R and c must hold one rotation and one centre per view")
+        hp = None if has_pose is None else np.ascontiguousarray(np.asarray(has_pose) != 0, np.uint8)
+        if hp is not None and hp.size != V:
+            raise ValueError("has_pose must have one entry per view")
+        views = (L.KeypointView * max(V, 1))()
+        for v, kp in enumerate(keypoints):
+            views[v].d_xy, views[v].n = (kp["xy"].data_ptr() if kp["n"] else None), kp["n"]
+            views[v].fx, views[v].fy, views[v].cx, views[v].cy = kp["fx"], kp["fy"], kp["cx"], kp["cy"]
+        return views, Rh, ch, hp, V, prm
+
+    def _triangulate_outputs(self, T, M, err_rms, n_used, obs_state):
+        dev = self.device
+        return (torch.empty((T, 3), dtype=torch.float64, device=dev), torch.empty(T, dtype=torch.uint8, device=dev),
+                torch.empty(T, dtype=torch.float64, device=dev) if err_rms else None,
+                torch.empty(T, dtype=torch.int32, device=dev) if n_used else None,
+                torch.empty(M, dtype=torch.uint8, device=dev) if obs_state else None)
+
+    def triangulate_tracks(self, track_begin, members, keypoints, R, c, has_pose=None, err_rms=True, n_used=True,
+                           obs_state=True, **params):
+        """Sparse 3-D points of multi-view tracks (pgi_triangulate_tracks; specification tests/triangulate_spec.py).
+        track_begin [T + 1] and members [(view << 32 | keypoint)]: numpy arrays or device tensors (int32 / int64 bit
+        patterns); keypoints: one upload_keypoints() object per view; R [V,3,3] world->camera (rotation_average), c [V,3]
+        centres (translation_average); has_pose [V] or None = all.  params: min_views, refine_iters, max_drops, thr_px,
+        min_angle_deg.  err_rms / n_used / obs_state = False leaves that output out.  -> Triangulation."""
+        dev = self.device
+        if torch.is_tensor(track_begin):
+            tb = track_begin.to(dev)
+        else:
+            tb = torch.from_numpy(np.array(track_begin, np.uint32).view(np.int32)).to(dev)
+        if torch.is_tensor(members):
+            mem = members.to(dev)
+        else:
+            mem = torch.from_numpy(np.array(members, np.uint64).view(np.int64)).to(dev)
+        if tb.element_size() != 4 or mem.element_size() != 8:
+            raise ValueError("track_begin must be 32-bit and members 64-bit")
+        T, M = max(int(tb.numel()) - 1, 0), int(mem.numel())
+        views, Rh, ch, hp, V, prm = self._triangulate_args(keypoints, R, c, has_pose, params)
+        X, status, err, nu, st = self._triangulate_outputs(T, M, err_rms, n_used, obs_state)
+        counts = np.zeros(L.TRI_STATUS_COUNT, np.uint32)
+        self._bind_stream()
+        L.check(self._lib.pgi_triangulate_tracks(
+            self._ctx, _ptr(tb) if T else None, _ptr(mem) if M else None, T, views, Rh.ctypes.data_as(C.c_void_p),
+            ch.ctypes.data_as(C.c_void_p), None if hp is None else hp.ctypes.data_as(C.c_void_p), V, C.byref(prm), _ptr(X),
+            _ptr(err), _ptr(nu), _ptr(status), _ptr(st) if M else None, counts.ctypes.data_as(C.c_void_p)))
+        return Triangulation(X, status, err, nu, st, counts)
+
     # ---- multi-GPU exchange (include/pgi.h: pgi_comm_*, pgi_allgather_edges) ----------------------------------------
     def comm_info(self):
         w, r, k = C.c_uint32(1), C.c_uint32(0), C.c_uint32(0)
@@ -516,6 +593,22 @@ class DeviceTracklets:
 
     def get_correspondences(self, src, dst, max_n):
         return self.get_correspondences_batch([(src, dst)], max_n)[0]
+
+    def triangulate(self, keypoints, R, c, has_pose=None, err_rms=True, n_used=True, obs_state=True, **params):
+        """Engine.triangulate_tracks on the store's current by-track ordering (pgi_tracklets_triangulate): track indices
+        and member order are those of track(); no member leaves the device.  -> Triangulation."""
+        eng = self.eng
+        i = self.info()
+        T, M = i["tracks"], i["events"]
+        views, Rh, ch, hp, V, prm = eng._triangulate_args(keypoints, R, c, has_pose, params)
+        X, status, err, nu, st = eng._triangulate_outputs(T, M, err_rms, n_used, obs_state)
+        counts = np.zeros(L.TRI_STATUS_COUNT, np.uint32)
+        eng._bind_stream()
+        L.check(self._lib.pgi_tracklets_triangulate(
+            self._t, views, Rh.ctypes.data_as(C.c_void_p), ch.ctypes.data_as(C.c_void_p),
+            None if hp is None else hp.ctypes.data_as(C.c_void_p), V, C.byref(prm), _ptr(X), _ptr(err), _ptr(nu), _ptr(status),
+            _ptr(st) if M else None, counts.ctypes.data_as(C.c_void_p)))
+        return Triangulation(X, status, err, nu, st, counts)
 
     def info(self):
         a, b, r = C.c_uint64(), C.c_uint64(), C.c_uint32()
