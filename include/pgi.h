@@ -288,15 +288,16 @@ typedef struct {
     double weight;      /* >= 0, e.g. the inlier ratio */
 } pgi_trans_edge;
 typedef struct {
-    uint32_t iters;     /* 60    outer iterations                                   */
-    uint32_t cg_iters;  /* 200   cap of the inner PCG                               */
+    uint32_t iters;     /* 60    outer iterations; 0 returns the initialisation     */
+    uint32_t cg_iters;  /* 200   cap of the inner PCG; 0 is taken as 1              */
     double eps;         /* 1e-3  proximal weight along dir on free edges, in (0, 1] */
     double delta;       /* 1e-4  floor of the residual in the L1 weight             */
     double tol;         /* 1e-9  mean step over the views                           */
 } pgi_transavg_params;
 void pgi_default_transavg_params(pgi_transavg_params* p);
 /* h_* host pointers; h_c_out: n_views x 3.  A vertex id >= n_views, src == dst, a zero or non-finite dir or a
- * negative weight return PGI_ERR_INVALID; zero edges give all-zero positions.  Synchronous. */
+ * negative weight return PGI_ERR_INVALID, and so do eps outside (0, 1], delta <= 0 and tol < 0; zero edges give
+ * all-zero positions.  Synchronous. */
 int pgi_translation_average(pgi_ctx* ctx, const pgi_trans_edge* h_edges, uint32_t n_edges, uint32_t n_views,
                             const pgi_transavg_params* prm, double* h_c_out /* n_views x 3 */, uint32_t* h_iters_out);
 /* The same solve fed from the DEVICE-resident edge table (what pgi_rotation_average_edges takes) and the global
