@@ -524,6 +524,63 @@ int pgi_tracklets_triangulate(pgi_tracklets* trk, const pgi_keypoint_view* h_vie
                               double* d_err, uint32_t* d_n_used, uint8_t* d_status, uint8_t* d_obs_state,
                               uint32_t* h_status_counts);
 
+/* ---- bundle adjustment: joint refinement of poses and 3-D points (not in the reference) ----
+ * Levenberg-Marquardt on the pixel reprojection error over the poses (R, c) and the points X together, Huber IRLS
+ * weights, Marquardt damping H + lambda diag(H).  The normal equations are solved in Schur form by Schur-Jacobi
+ * preconditioned CG on the reduced camera system, which is never formed: its product is two passes over the
+ * per-observation Jacobian records (per point, then per camera).  The specification is tests/bundle_spec.py (DESIGN.md
+ * section 3, item 11).  f64 throughout, no floating-point atomics, every sum in a fixed order: the same input gives the
+ * same bits.
+ * Participation: a member of track t takes part when d_obs_state is 1, d_status[t] is PGI_TRI_OK (or PGI_TRI_LOW_PARALLAX
+ * with use_low_parallax), X[t] is finite and its view has a pose; a track with fewer than two such members is left alone.
+ * A view is FREE when it has a pose, is not marked in h_fixed and has at least min_cam_obs participating observations;
+ * every other posed view is held and still constrains its points.
+ * Gauge: with h_fixed == NULL the smallest-index posed view that has participating observations is held.  What remains
+ * (the scale, and the frames of further components) is left to the damping, lambda > 0 always: the cost is invariant
+ * under the gauge, so its gradient has no component along it and the damped step does not move along it. */
+#define PGI_BA_STOP_ITERS 0   /* the iteration limit                                   */
+#define PGI_BA_STOP_FTOL 1    /* an accepted step lowered the cost by less than ftol   */
+#define PGI_BA_STOP_LAMBDA 2  /* lambda passed its cap (1e12) after rejected steps     */
+#define PGI_BA_STOP_EMPTY 3   /* no participating observation: nothing to do           */
+typedef struct {
+    uint32_t iters;            /* 20    outer (Levenberg-Marquardt) iterations                              */
+    uint32_t cg_iters;         /* 200   PCG iterations per outer iteration                                  */
+    uint32_t min_cam_obs;      /* 8     participating observations a view needs to be free                  */
+    uint32_t use_low_parallax; /* 0     also refine PGI_TRI_LOW_PARALLAX tracks                             */
+    double huber_px;           /* 4.0   Huber threshold on the reprojection error, pixels; +inf = least squares */
+    double cg_tol;             /* 1e-6  PCG stops at this relative residual (preconditioner norm)           */
+    double ftol;               /* 1e-9  stop when an accepted step's relative cost decrease is below        */
+    double lambda_init;        /* 1e-4  first damping factor                                                */
+} pgi_bundle_params;
+void pgi_default_bundle_params(pgi_bundle_params* p);
+typedef struct {
+    uint32_t iters;          /* outer iterations run                      */
+    uint32_t accepted;       /* steps accepted                            */
+    uint32_t cg_iters_total; /* PCG iterations over all outer iterations  */
+    uint32_t stop_reason;    /* PGI_BA_STOP_*                             */
+    uint32_t n_obs;          /* participating observations                */
+    uint32_t n_points;       /* participating tracks                      */
+    uint32_t n_free_cams;    /* free views                                */
+    uint32_t reserved;
+    double cost_initial, cost_final; /* sum of rho over the participating observations */
+    double lambda_final;
+} pgi_bundle_report;
+/* Tracks, members, views, h_R, h_c and h_has_pose as in pgi_triangulate_tracks; d_status and d_obs_state as written by
+ * it; h_fixed: n_views bytes or NULL.  In-out: h_R, h_c (host; only free views change) and d_X (device; only participating
+ * tracks change).  Synchronous.  An empty participation set succeeds and changes nothing.  PGI_ERR_INVALID: a NULL
+ * argument, a non-finite pose or non-positive fx / fy of a view that has a pose, parameters out of range (huber_px <= 0,
+ * cg_tol or lambda_init <= 0), or a non-positive depth of a participating observation at the start (nothing is
+ * written).  At a trial point a non-positive depth rejects the step.  report may be NULL. */
+int pgi_bundle_adjust(pgi_ctx* ctx, const uint32_t* d_track_begin, const uint64_t* d_members, uint32_t n_tracks,
+                      const pgi_keypoint_view* h_views, double* h_R, double* h_c, const uint8_t* h_has_pose,
+                      const uint8_t* h_fixed, uint32_t n_views, const pgi_bundle_params* prm, double* d_X,
+                      const uint8_t* d_status, const uint8_t* d_obs_state, pgi_bundle_report* report);
+/* The same on the store's current by-track ordering, mirroring pgi_tracklets_triangulate. */
+int pgi_tracklets_bundle_adjust(pgi_tracklets* trk, const pgi_keypoint_view* h_views, double* h_R, double* h_c,
+                                const uint8_t* h_has_pose, const uint8_t* h_fixed, uint32_t n_views,
+                                const pgi_bundle_params* prm, double* d_X, const uint8_t* d_status,
+                                const uint8_t* d_obs_state, pgi_bundle_report* report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,12 @@ struct pgi_ctx {
     void* h_tri_stage = nullptr;
     size_t tri_stage_bytes = 0;
     hipEvent_t tri_stage_ev = nullptr;
+    // bundle adjustment (pgi_bundle.hip): grow-only device scratch of the preparation (per-track counts, offsets, scan)
+    // and of the solve (observation records in both orders, point and camera vectors, saved state)
+    void* d_ba_prep = nullptr;
+    size_t ba_prep_bytes = 0;
+    void* d_ba_ws = nullptr;
+    size_t ba_ws_bytes = 0;
 };
 
 struct pgi_tracklets;

@@ -1853,6 +1853,8 @@ void pgi_destroy(pgi_ctx* ctx) {
     if (ctx->d_tri_ws) (void)hipFree(ctx->d_tri_ws);
     if (ctx->h_tri_stage) (void)hipHostFree(ctx->h_tri_stage);
     if (ctx->tri_stage_ev) (void)hipEventDestroy(ctx->tri_stage_ev);
+    if (ctx->d_ba_prep) (void)hipFree(ctx->d_ba_prep);
+    if (ctx->d_ba_ws) (void)hipFree(ctx->d_ba_ws);
     if (ctx->d_bucket) (void)hipFree(ctx->d_bucket);
     for (int k = 0; k < 4; ++k) {
         if (ctx->hslot[k].d) (void)hipFree(ctx->hslot[k].d);

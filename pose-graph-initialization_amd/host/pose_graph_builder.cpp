@@ -1854,6 +1854,81 @@ PoseGraphBuilder::TriangulatedPoints PoseGraphBuilder::triangulateTracks(const T
     return triangulateTracks(begin, members, views, rotations_, positions_, hasPose, params);
 }
 
+PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjust(const std::vector<uint32_t>& trackBegin, const std::vector<uint64_t>& members,
+                                                                  const std::vector<ViewFeaturesRef>& views,
+                                                                  const GlobalRotations& rotations_, const GlobalPositions& positions_,
+                                                                  const TriangulatedPoints& points_, const std::vector<uint8_t>* hasPose,
+                                                                  const std::vector<uint8_t>* fixed, const pgi_bundle_params* params) {
+    BundleAdjustment out;
+    out.rotations = rotations_;
+    out.positions = positions_;
+    out.points = points_.points;
+    out.report.stop_reason = PGI_BA_STOP_EMPTY;
+    const size_t V = views.size(), T = trackBegin.empty() ? 0 : trackBegin.size() - 1, M = members.size();
+    if (rotations_.rotations.size() != V || positions_.positions.size() != V)
+        throw std::invalid_argument("bundleAdjust: one global rotation and one position per view are needed");
+    if ((hasPose && hasPose->size() != V) || (fixed && fixed->size() != V)) throw std::invalid_argument("bundleAdjust: one flag per view is needed");
+    if (T && trackBegin.back() != M) throw std::invalid_argument("bundleAdjust: the last offset must be the member count");
+    if (points_.points.size() != T || points_.status.size() != T || points_.observationState.size() != M)
+        throw std::invalid_argument("bundleAdjust: points, status and observation states must match the tracks");
+    if (!T || !V) return out;
+    pgi_ctx* ctx = engine->get();
+    HIP_OK(hipSetDevice(engineDevice(ctx)));
+    struct Block {  // one device block: keypoints, offsets, members, points, status, states
+        void* p = nullptr;
+        ~Block() { if (p) (void)hipFree(p); }
+    } block;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    std::vector<size_t> kpOff(V + 1, 0);
+    for (size_t v = 0; v < V; ++v) kpOff[v + 1] = kpOff[v] + up(views[v].size() * 8);
+    const size_t oBegin = kpOff[V], oMem = oBegin + up((T + 1) * 4), oX = oMem + up(M * 8), oStatus = oX + up(T * 24), oState = oStatus + up(T),
+                 total = oState + up(M);
+    HIP_OK(hipMalloc(&block.p, total));
+    char* d = (char*)block.p;
+    hipStream_t s = engineStream(ctx);
+    std::vector<pgi_keypoint_view> kv(V);
+    std::vector<double> R(V * 9), c(V * 3);
+    for (size_t v = 0; v < V; ++v) {
+        const size_t n = views[v].size();
+        if (n) {
+            if (!views[v].keypoints) throw PgiError("bundleAdjust: null keypoint array");
+            HIP_OK(hipMemcpyAsync(d + kpOff[v], views[v].keypoints, n * 8, hipMemcpyHostToDevice, s));
+        }
+        kv[v] = pgi_keypoint_view{n ? (const float*)(d + kpOff[v]) : nullptr, (uint32_t)n, 0, views[v].focalLength, views[v].focalLength,
+                                  views[v].width / 2.0, views[v].height / 2.0};
+        std::memcpy(&R[v * 9], rotations_.rotations[v].data(), 72);
+        std::memcpy(&c[v * 3], positions_.positions[v].data(), 24);
+    }
+    HIP_OK(hipMemcpyAsync(d + oBegin, trackBegin.data(), (T + 1) * 4, hipMemcpyHostToDevice, s));
+    if (M) HIP_OK(hipMemcpyAsync(d + oMem, members.data(), M * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d + oX, points_.points[0].data(), T * 24, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d + oStatus, points_.status.data(), T, hipMemcpyHostToDevice, s));
+    if (M) HIP_OK(hipMemcpyAsync(d + oState, points_.observationState.data(), M, hipMemcpyHostToDevice, s));
+    Engine::check(pgi_bundle_adjust(ctx, (const uint32_t*)(d + oBegin), (const uint64_t*)(d + oMem), (uint32_t)T, kv.data(), R.data(), c.data(),
+                                    hasPose ? hasPose->data() : nullptr, fixed ? fixed->data() : nullptr, (uint32_t)V, params,
+                                    (double*)(d + oX), (const uint8_t*)(d + oStatus), (const uint8_t*)(d + oState), &out.report));
+    HIP_OK(hipMemcpyAsync(out.points[0].data(), d + oX, T * 24, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    for (size_t v = 0; v < V; ++v) {
+        std::memcpy(out.rotations.rotations[v].data(), &R[v * 9], 72);
+        std::memcpy(out.positions.positions[v].data(), &c[v * 3], 24);
+    }
+    return out;
+}
+
+PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjust(const Tracklets& tracks_, const std::vector<ViewFeaturesRef>& views,
+                                                                  const GlobalRotations& rotations_, const GlobalPositions& positions_,
+                                                                  const TriangulatedPoints& points_, const std::vector<uint8_t>* hasPose,
+                                                                  const std::vector<uint8_t>* fixed, const pgi_bundle_params* params) {
+    std::vector<uint32_t> begin(1, 0);
+    std::vector<uint64_t> members;
+    for (size_t t = 0; t < tracks_.trackNumber(); ++t) {
+        for (const Tracklets::Pair& m : tracks_.track(t)) members.push_back(((uint64_t)m.first << 32) | (uint64_t)(uint32_t)m.second);
+        begin.push_back((uint32_t)members.size());
+    }
+    return bundleAdjust(begin, members, views, rotations_, positions_, points_, hasPose, fixed, params);
+}
+
 namespace pose {
 // pose_utils.h:172-252 -- one re-entrant call on host pointers (pgi_pose_from_essential_host: private slot of the context,
 // no allocation once warm); every row votes, as in the reference (:203)

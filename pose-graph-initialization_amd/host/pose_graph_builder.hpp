@@ -826,6 +826,27 @@ class PoseGraphBuilder {  // include/pose_graph_builder.h:25-171
                                          const GlobalRotations& rotations_, const GlobalPositions& positions_,
                                          const std::vector<uint8_t>* hasPose = nullptr, const pgi_triangulate_params* params = nullptr);
 
+    // Joint refinement of the global poses and the triangulated points (include/pgi.h: pgi_bundle_adjust; specification
+    // tests/bundle_spec.py).  points_: what triangulateTracks returned for the same tracks, views and poses (points, status,
+    // observationState).  fixed: views to hold (null: the first posed view with observations holds the gauge).  The builder
+    // keeps no device store after processFeatures, so the call takes arrays or a host store and makes one round trip.
+    struct BundleAdjustment {
+        GlobalRotations rotations;     // refined where the view was free
+        GlobalPositions positions;
+        std::vector<Vector3d> points;  // refined where the track took part
+        pgi_bundle_report report{};
+    };
+    BundleAdjustment bundleAdjust(const std::vector<uint32_t>& trackBegin, const std::vector<uint64_t>& members,
+                                  const std::vector<ViewFeaturesRef>& views, const GlobalRotations& rotations_,
+                                  const GlobalPositions& positions_, const TriangulatedPoints& points_,
+                                  const std::vector<uint8_t>* hasPose = nullptr, const std::vector<uint8_t>* fixed = nullptr,
+                                  const pgi_bundle_params* params = nullptr);
+    // The same for a host-only store (host/tracklets.hpp), in track order.
+    BundleAdjustment bundleAdjust(const class Tracklets& tracks_, const std::vector<ViewFeaturesRef>& views,
+                                  const GlobalRotations& rotations_, const GlobalPositions& positions_,
+                                  const TriangulatedPoints& points_, const std::vector<uint8_t>* hasPose = nullptr,
+                                  const std::vector<uint8_t>* fixed = nullptr, const pgi_bundle_params* params = nullptr);
+
     struct RunStatistics {  // the reference's RunningStatistics keys that concern this path (utils.h:15-73)
         size_t pairsProcessed = 0, edgesAdded = 0, pathsSearched = 0, pathsFound = 0, touchedNodes = 0,
                posesFromGuess = 0, hypotheses = 0, waves = 0;

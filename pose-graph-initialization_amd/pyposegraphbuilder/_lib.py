@@ -55,6 +55,22 @@ class TriangulateParams(C.Structure):
                 ("thr_px", C.c_double), ("min_angle_deg", C.c_double)]
 
 
+class BundleParams(C.Structure):
+    """pgi_bundle_params (include/pgi.h)."""
+    _fields_ = [("iters", C.c_uint32), ("cg_iters", C.c_uint32), ("min_cam_obs", C.c_uint32), ("use_low_parallax", C.c_uint32),
+                ("huber_px", C.c_double), ("cg_tol", C.c_double), ("ftol", C.c_double), ("lambda_init", C.c_double)]
+
+
+class BundleReport(C.Structure):
+    """pgi_bundle_report (include/pgi.h)."""
+    _fields_ = [("iters", C.c_uint32), ("accepted", C.c_uint32), ("cg_iters_total", C.c_uint32), ("stop_reason", C.c_uint32),
+                ("n_obs", C.c_uint32), ("n_points", C.c_uint32), ("n_free_cams", C.c_uint32), ("reserved", C.c_uint32),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double), ("lambda_final", C.c_double)]
+
+
+# why the bundle adjustment stopped (PGI_BA_STOP_* of include/pgi.h)
+BA_STOP_ITERS, BA_STOP_FTOL, BA_STOP_LAMBDA, BA_STOP_EMPTY = range(4)
+
 # per-track status of the triangulation (PGI_TRI_* of include/pgi.h)
 TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_BEHIND, TRI_REPROJ, TRI_LOW_PARALLAX = range(6)
 TRI_STATUS_COUNT = 6
@@ -80,7 +96,8 @@ SYMBOLS = ["pgi_last_error", "pgi_device_count", "pgi_default_params", "pgi_crea
            "pgi_tracklets_create", "pgi_tracklets_destroy", "pgi_tracklets_add_batch", "pgi_tracklets_get_batch",
            "pgi_tracklets_info", "pgi_tracklets_track",
            "pgi_default_transavg_params", "pgi_translation_average", "pgi_translation_average_edges",
-           "pgi_default_triangulate_params", "pgi_triangulate_tracks", "pgi_tracklets_triangulate"]
+           "pgi_default_triangulate_params", "pgi_triangulate_tracks", "pgi_tracklets_triangulate",
+           "pgi_default_bundle_params", "pgi_bundle_adjust", "pgi_tracklets_bundle_adjust"]
 COMM_ID_BYTES = 128
 # pgi_allgatherv_fn: int (*)(void* user, const void* send, uint64 send_bytes, void* recv, const uint64* recv_bytes, uint32 world)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32)
@@ -196,6 +213,12 @@ def load():
     view_args = [C.POINTER(KeypointView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(TriangulateParams)]
     lib.pgi_triangulate_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + view_args + [C.c_void_p] * 6
     lib.pgi_tracklets_triangulate.argtypes = [C.c_void_p] + view_args + [C.c_void_p] * 6
+    lib.pgi_default_bundle_params.restype = None
+    lib.pgi_default_bundle_params.argtypes = [C.POINTER(BundleParams)]
+    ba_args = [C.POINTER(KeypointView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(BundleParams),
+               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BundleReport)]
+    lib.pgi_bundle_adjust.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + ba_args
+    lib.pgi_tracklets_bundle_adjust.argtypes = [C.c_void_p] + ba_args
     _lib = lib
     return lib
 

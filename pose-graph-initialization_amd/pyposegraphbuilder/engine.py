@@ -31,6 +31,23 @@ class Triangulation:
                     obs_state=f(self.obs_state), counts=self.counts.copy())
 
 
+class BundleResult:
+    """Result of Engine.bundle_adjust / DeviceTracklets.bundle_adjust: R [V,3,3] and c [V,3] (numpy, refined where the view
+    was free), X [T,3] f64 (device tensor, refined where the track took part) and the fields of pgi_bundle_report: iters,
+    accepted, cg_iters_total, stop_reason (pyposegraphbuilder.BA_STOP_*), n_obs, n_points, n_free_cams, cost_initial,
+    cost_final, lambda_final."""
+    FIELDS = ("iters", "accepted", "cg_iters_total", "stop_reason", "n_obs", "n_points", "n_free_cams", "cost_initial",
+              "cost_final", "lambda_final")
+
+    def __init__(self, R, c, X, report):
+        self.R, self.c, self.X = R, c, X
+        for k in self.FIELDS:
+            setattr(self, k, getattr(report, k))
+
+    def report(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+
 class Engine:
     def __init__(self, device=None, **params):
         lib = L.load()
@@ -378,6 +395,48 @@ class Engine:
             _ptr(err), _ptr(nu), _ptr(status), _ptr(st) if M else None, counts.ctypes.data_as(C.c_void_p)))
         return Triangulation(X, status, err, nu, st, counts)
 
+    # ---- bundle adjustment -------------------------------------------------------------------------
+    def _bundle_args(self, keypoints, R, c, X, status, obs_state, has_pose, fixed, T, M, kw):
+        """-> the arguments pgi_bundle_adjust and pgi_tracklets_bundle_adjust share, and what must outlive the call."""
+        prm = L.BundleParams()
+        self._lib.pgi_default_bundle_params(C.byref(prm))
+        for k, v in kw.items():
+            if not hasattr(prm, k):
+                raise TypeError("unknown parameter %r" % k)
+            setattr(prm, k, v)
+        views, Rh, ch, hp, V, _ = self._triangulate_args(keypoints, R, c, has_pose, {})
+        Rh, ch = Rh.copy(), ch.copy()  # in-out: the caller's arrays stay as they are
+        fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8)
+        if fx is not None and fx.size != V:
+            raise ValueError("fixed must have one entry per view")
+        dev = self.device
+        Xd = (X.to(dev, torch.float64) if torch.is_tensor(X) else torch.from_numpy(np.array(X, np.float64)).to(dev)).reshape(-1, 3).clone()
+        st = status.to(dev) if torch.is_tensor(status) else torch.from_numpy(np.array(status, np.uint8)).to(dev)
+        ob = obs_state.to(dev) if torch.is_tensor(obs_state) else torch.from_numpy(np.array(obs_state, np.uint8)).to(dev)
+        if Xd.shape[0] != T or st.numel() != T or ob.numel() != M or st.element_size() != 1 or ob.element_size() != 1:
+            raise ValueError("X [T,3], status [T] and obs_state [members] (bytes) must match the tracks")
+        rep = L.BundleReport()
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        args = (views, ptr(Rh), ptr(ch), ptr(hp), ptr(fx), V, C.byref(prm), _ptr(Xd) if T else None, _ptr(st) if T else None,
+                _ptr(ob) if M else None, C.byref(rep))
+        return args, (Rh.reshape(V, 3, 3), ch.reshape(V, 3), Xd, rep), (views, hp, fx, st, ob, prm)
+
+    def bundle_adjust(self, track_begin, members, keypoints, R, c, X, status, obs_state, has_pose=None, fixed=None, **params):
+        """Joint refinement of poses and points (pgi_bundle_adjust; specification tests/bundle_spec.py).  Tracks, keypoints,
+        R, c and has_pose as in triangulate_tracks; X, status and obs_state as it returned them (arrays or device tensors);
+        fixed [V] or None = the first posed view with observations holds the gauge.  params: iters, cg_iters, min_cam_obs,
+        use_low_parallax, huber_px, cg_tol, ftol, lambda_init.  The inputs are not modified.  -> BundleResult."""
+        dev = self.device
+        tb = track_begin.to(dev) if torch.is_tensor(track_begin) else torch.from_numpy(np.array(track_begin, np.uint32).view(np.int32)).to(dev)
+        mem = members.to(dev) if torch.is_tensor(members) else torch.from_numpy(np.array(members, np.uint64).view(np.int64)).to(dev)
+        if tb.element_size() != 4 or mem.element_size() != 8:
+            raise ValueError("track_begin must be 32-bit and members 64-bit")
+        T, M = max(int(tb.numel()) - 1, 0), int(mem.numel())
+        args, (Rh, ch, Xd, rep), keep = self._bundle_args(keypoints, R, c, X, status, obs_state, has_pose, fixed, T, M, params)
+        self._bind_stream()
+        L.check(self._lib.pgi_bundle_adjust(self._ctx, _ptr(tb) if T else None, _ptr(mem) if M else None, T, *args))
+        return BundleResult(Rh, ch, Xd, rep)
+
     # ---- multi-GPU exchange (include/pgi.h: pgi_comm_*, pgi_allgather_edges) ----------------------------------------
     def comm_info(self):
         w, r, k = C.c_uint32(1), C.c_uint32(0), C.c_uint32(0)
@@ -609,6 +668,16 @@ class DeviceTracklets:
             None if hp is None else hp.ctypes.data_as(C.c_void_p), V, C.byref(prm), _ptr(X), _ptr(err), _ptr(nu), _ptr(status),
             _ptr(st) if M else None, counts.ctypes.data_as(C.c_void_p)))
         return Triangulation(X, status, err, nu, st, counts)
+
+    def bundle_adjust(self, keypoints, R, c, X, status, obs_state, has_pose=None, fixed=None, **params):
+        """Engine.bundle_adjust on the store's current by-track ordering (pgi_tracklets_bundle_adjust), e.g. with the X,
+        status and obs_state of triangulate(); no member leaves the device.  -> BundleResult."""
+        eng = self.eng
+        i = self.info()
+        args, (Rh, ch, Xd, rep), keep = eng._bundle_args(keypoints, R, c, X, status, obs_state, has_pose, fixed, i["tracks"], i["events"], params)
+        eng._bind_stream()
+        L.check(self._lib.pgi_tracklets_bundle_adjust(self._t, *args))
+        return BundleResult(Rh, ch, Xd, rep)
 
     def info(self):
         a, b, r = C.c_uint64(), C.c_uint64(), C.c_uint32()
