@@ -1598,6 +1598,9 @@ static int rotavg_solve(pgi_ctx* ctx, const pgi_rotavg_params& prm_in, uint32_t 
     const bool trace = std::getenv("PGI_ROTAVG_TRACE") != nullptr;
     pgi_rotavg_params prm = prm_in;
     if (const char* e = std::getenv("PGI_ROTAVG_CG_ITERS")) prm.cg_iters = (uint32_t)std::max(1, std::atoi(e));  // experiments
+    // iteration cap of the tree-preconditioned kernel; PGI_ROTAVG_TREE_CG_ITERS replaces it (tests: a fixed number of steps)
+    uint32_t tree_cg_iters = std::max<uint32_t>(prm.cg_iters, 1000u);
+    if (const char* e = std::getenv("PGI_ROTAVG_TREE_CG_ITERS")) tree_cg_iters = (uint32_t)std::max(1, std::atoi(e));  // experiments
     const double sigma = prm.sigma_deg * 3.14159265358979323846 / 180.0;
     uint32_t iters = 0;
     uint32_t predicted = 0;   // PCG iterations of the previous outer step's solve (multi-workgroup Jacobi branch)
@@ -1810,7 +1813,7 @@ static int rotavg_solve(pgi_ctx* ctx, const pgi_rotavg_params& prm_in, uint32_t 
                                (const uint32_t*)(d + o_tedge), (const uint32_t*)(d + o_tother), (const int8_t*)(d + o_tsign),
                                (const uint32_t*)(d + o_tpe), (const uint32_t*)(d + o_tsz), (const uint32_t*)(d + o_ten),
                                (const uint32_t*)(d + o_tex), (const uint32_t*)(d + o_tn2o), (const double*)(d + o_omega),
-                               (const double*)(d + o_w), std::max<uint32_t>(prm.cg_iters, 1000u), cg_tol, (TreeIncidence*)(d + o_aw),
+                               (const double*)(d + o_w), tree_cg_iters, cg_tol, (TreeIncidence*)(d + o_aw),
                                (double*)(d + o_x), (double*)(d + o_its));
         };
         // multi-workgroup Jacobi PCG: 1 = converged (and applied: finish_views ran on the record), 0 = not, < 0 on an error

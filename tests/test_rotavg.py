@@ -7,6 +7,7 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
 import rotavg_oracle as RO  # noqa: E402
+from rotavg_pcg_ref import sequence_graph  # noqa: E402
 
 
 def test_oracle_exact_on_noise_free_graph():
@@ -95,29 +96,6 @@ def test_hip_rotation_averaging_matches_oracle(V, k, noise, outl, comps):
     if comps == 1:
         assert RO.align_error_deg(R, Rgt).mean() < max(0.05, noise)
     eng.close()
-
-
-def sequence_graph(V, reach, noise_deg, outlier_frac, seed, components=1):
-    """An image-sequence view graph: view i sees views i+1 .. i+reach (per component), like a video or a walk-through.
-    Its Laplacian is banded: Jacobi-preconditioned CG needs ~(V / reach) iterations times a large constant."""
-    from scipy.spatial.transform import Rotation
-    rng = np.random.default_rng(seed)
-    Rgt = Rotation.random(V, random_state=seed).as_matrix()
-    src, dst = [], []
-    for c in range(components):
-        idx = np.arange(c, V, components)
-        for a in range(len(idx)):
-            for s_ in range(1, reach + 1):
-                if a + s_ < len(idx):
-                    i, j = (idx[a], idx[a + s_]) if rng.random() < 0.5 else (idx[a + s_], idx[a])
-                    src.append(i); dst.append(j)
-    src, dst = np.array(src), np.array(dst)
-    Rrel = np.einsum("eij,ekj->eik", Rgt[dst], Rgt[src])
-    Rrel = np.einsum("eij,ejk->eik", Rotation.from_rotvec(rng.standard_normal((len(src), 3)) * np.deg2rad(noise_deg) / np.sqrt(3)).as_matrix(), Rrel)
-    out = rng.random(len(src)) < outlier_frac
-    Rrel[out] = Rotation.random(int(out.sum()), random_state=seed + 1).as_matrix()
-    w = np.where(out, rng.uniform(0.1, 0.4, len(src)), rng.uniform(0.4, 1.0, len(src)))
-    return src, dst, Rrel, w, Rgt
 
 
 @pytest.mark.gpu
