@@ -344,10 +344,11 @@ def make_descriptors(rng, n_a, n_b, overlap=0.6, noise=0.05, dim=128, duplicates
 
 
 def make_feature_views(rng, n_views=3, n_points=1500, n_clutter=500, f=1000.0, w=1600.0, h=1200.0, desc_noise=0.04,
-                       px_noise=0.3):
+                       px_noise=0.3, with_points=False):
     """A small scene seen by n_views cameras: every view detects a random ~75% of the 3-D points (pixel keypoints +
     a noisy copy of the point's RootSIFT-like descriptor) plus unmatched clutter.  Returns views[v] = dict(xy, desc,
-    point_id) and the ground-truth world->camera poses."""
+    point_id) and the ground-truth world->camera poses (R, t): x_cam = R X + t, pixel = f x_cam / z_cam + (w/2, h/2).
+    with_points: the 3-D points [n_points, 3] (row = point_id) are returned as a fourth value."""
     def unit(x):
         x = np.abs(x).astype(np.float32)
         return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
@@ -371,6 +372,8 @@ def make_feature_views(rng, n_views=3, n_points=1500, n_clutter=500, f=1000.0, w
                           desc=np.concatenate([desc, cdesc])[perm].astype(np.float32),
                           point_id=np.concatenate([ids, -np.ones(n_clutter, np.int64)])[perm]))
         poses.append((R, t))
+    if with_points:
+        return views, poses, (f, w, h), X
     return views, poses, (f, w, h)
 
 

@@ -65,11 +65,7 @@ def spec_result(V, T):
     return freeze(TS.triangulate(tb, mem, problem(V)["views"]))
 
 
-def assert_same(got, want, what=""):
-    for k in ("status", "n_used", "obs_state", "counts", "X", "err_rms"):
-        a, b = np.asarray(got[k]), np.asarray(want[k])
-        assert a.shape == b.shape, (what, k)
-        assert np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), (what, k, np.nonzero(~((a == b) | ((a != a) & (b != b))))[0][:8])
+assert_same = TS.assert_same   # (shared with tests/test_chain.py)
 
 
 # ---- CPU ----------------------------------------------------------------------------------------------------------

@@ -263,6 +263,14 @@ def triangulate(track_begin, members, views, min_views=2, refine_iters=3, thr_px
                 counts=np.bincount(status, minlength=N_STATUS).astype(np.uint32))
 
 
+def assert_same(got, want, what=""):
+    """Two results of triangulate (or of the device call, as numpy) hold the same bits, NaNs in the same places."""
+    for k in ("status", "n_used", "obs_state", "counts", "X", "err_rms"):
+        a, b = np.asarray(got[k]), np.asarray(want[k])
+        assert a.shape == b.shape, (what, k)
+        assert np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), (what, k, np.nonzero(~((a == b) | ((a != a) & (b != b))))[0][:8])
+
+
 # ---- scenes -------------------------------------------------------------------------------------------------------
 def _rodrigues(w):
     th = np.linalg.norm(w, axis=1)
