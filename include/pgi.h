@@ -41,6 +41,7 @@ typedef enum {
 #define PGI_EDGE_NAN (-1)          /* false (pose_graph_builder.h:1069-1070)             */
 #define PGI_EDGE_FEW_POINTS (-2)   /* fewer than 5 rows                                  */
 #define PGI_EDGE_TOO_MANY_ROWS (-3) /* the pair has more rows than pgi_batch.max_corr promised */
+#define PGI_EDGE_INCONSISTENT (-4) /* was PGI_EDGE_OK; dropped by the cycle-consistency filter (pgi_cycle_filter_edges)  */
 
 typedef struct pgi_ctx pgi_ctx;
 
@@ -309,6 +310,57 @@ int pgi_translation_average_edges(pgi_ctx* ctx, const pgi_edge* d_edges, const u
                                   const uint32_t* h_rows, uint32_t n_pairs, uint32_t n_views, const double* h_R_global,
                                   const pgi_transavg_params* prm, double* h_c_out, uint32_t* h_iters_out,
                                   uint32_t* h_edges_used);
+
+/* ---- cycle-consistency edge filter: triplet checks before the averaging (not in the reference) ----
+ * Loop closure over the triangles of the view graph, as the global pipelines do before they average.  The specification is
+ * tests/cycle_spec.py; every output is an integer and equals it exactly.
+ * A triangle is three views a < b < c with a PGI_EDGE_OK record on each of the three unordered pairs, in either
+ * orientation; every record gives its pose in the direction needed, as stored or inverted (R^T, -R^T t).  It is GOOD when
+ *   trace(R_ac R_cb R_ba) >= 1 + 2 cos(rot_thr)   (the loop rotation is within rot_thr of the identity), and,
+ *   with u1 = R_ba^T t_ba, u2 = R_ba^T R_cb^T t_cb, u3 = t_ac (the directions of c_a - c_b, c_b - c_c, c_c - c_a in frame a)
+ *   and n = u1 x u2: |n|^2 < sin^2(collinear_thr) (centres nearly collinear: no translation test), or
+ *   (u3 . n)^2 <= sin^2(trn_thr) |n|^2, (u2 x u3) . n > 0 and (u3 x u1) . n > 0 (coplanar, closing with positive scales).
+ * Per pair: n_tri triangles contain it, n_good of them good (both 0 for a record that is not OK).  A record is KEPT when it
+ * is OK and n_good >= min_good, or it is OK, n_tri == 0 and keep_untested is set (a bridge lies in no triangle).
+ * PGI_ERR_INVALID: a threshold outside (0, 90] degrees, min_good == 0, and among the OK records a view id >= n_views,
+ * src == dst or an unordered view pair that occurs twice.  Zero pairs, or no OK record, succeed with all-zero outputs.
+ * The adjacency of the OK records is built on the host (from h_src / h_dst and the 4-byte status column); the triangles
+ * are enumerated and evaluated on the device in f64, straight from the records.  Deterministic. */
+typedef struct {
+    double rot_thr_deg;        /* 5    loop rotation                                                     */
+    double trn_thr_deg;        /* 15   angle of the third direction out of the plane of the other two    */
+    double collinear_thr_deg;  /* 5    below this angle between two directions: rotation test only       */
+    uint32_t min_good;         /* 1    good triangles a record needs (never 0)                           */
+    uint32_t keep_untested;    /* 1    keep the OK records that lie in no triangle                       */
+} pgi_cycle_params;
+void pgi_default_cycle_params(pgi_cycle_params* p);
+typedef struct {
+    uint64_t n_triangles;            /* triangles of OK records                          */
+    uint64_t n_good;                 /* good ones among them                             */
+    uint64_t n_skipped_translation;  /* triangles judged by the rotation alone           */
+    uint32_t n_ok;                   /* PGI_EDGE_OK records that came in                 */
+    uint32_t n_dropped;              /* of those, not kept                               */
+} pgi_cycle_summary;
+typedef struct {
+    uint32_t src, dst;  /* x_dst = R x_src + t */
+    double R[9];
+    double t[3];        /* unit */
+} pgi_cycle_edge;
+/* Host arrays in (every edge takes part), host arrays out: h_keep (bytes), h_n_tri, h_n_good (n_edges each) and
+ * h_summary; each may be NULL.  Synchronous. */
+int pgi_cycle_filter(pgi_ctx* ctx, const pgi_cycle_edge* h_edges, uint32_t n_edges, uint32_t n_views,
+                     const pgi_cycle_params* prm, uint8_t* h_keep, uint32_t* h_n_tri, uint32_t* h_n_good,
+                     pgi_cycle_summary* h_summary);
+/* The same on the DEVICE-resident edge table the all-gather leaves on every rank: pair p = (h_src[p], h_dst[p]) with
+ * record d_edges[p]; only the R, t and status fields are read.  d_keep (n_pairs bytes), d_n_tri, d_n_good (n_pairs each;
+ * device) and h_summary (host): each may be NULL.  d_edges_out: NULL = no table is written; otherwise it receives the
+ * table with status = PGI_EDGE_INCONSISTENT on the OK records that were not kept and every other byte copied;
+ * d_edges_out == d_edges works in place (any other overlap is not allowed).  The written table goes unchanged into
+ * pgi_rotation_average_edges and pgi_translation_average_edges, which skip what is not PGI_EDGE_OK, and its status column
+ * is the mask for pgi_tracklets_add_batch.  Synchronous (the summary is on the host on return). */
+int pgi_cycle_filter_edges(pgi_ctx* ctx, const pgi_edge* d_edges, const uint32_t* h_src, const uint32_t* h_dst,
+                           uint32_t n_pairs, uint32_t n_views, const pgi_cycle_params* prm, uint8_t* d_keep,
+                           uint32_t* d_n_tri, uint32_t* d_n_good, pgi_cycle_summary* h_summary, pgi_edge* d_edges_out);
 
 /* ---- multi-GPU: the path's single exchange step -----------------------------------
  * Pairs are sharded over ranks (one process per GPU); every rank estimates its own block and the

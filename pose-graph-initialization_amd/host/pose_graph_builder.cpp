@@ -849,6 +849,46 @@ PoseGraphBuilder::GlobalPositions PoseGraphBuilder::averageTranslations(const pg
     return out;
 }
 
+PoseGraphBuilder::CycleFilterResult PoseGraphBuilder::filterEdgesByCycles(const PoseGraph& poseGraph_, size_t numViews,
+                                                                          const pgi_cycle_params* params) {
+    CycleFilterResult out;
+    std::vector<pgi_cycle_edge> ce(poseGraph_.numEdges());
+    poseGraph_.forEachEdge(0, ce.size(), [&](size_t k, const PoseGraphEdge& e) {
+        pgi_cycle_edge r{};
+        r.src = (uint32_t)e.getSourceId();
+        r.dst = (uint32_t)e.getDestinationId();
+        for (int c = 0; c < 9; ++c) r.R[c] = e.getValue().getRotation()[c];
+        for (int c = 0; c < 3; ++c) r.t[c] = e.getValue().getTranslation()[c];
+        ce[k] = r;
+    });
+    const size_t E = ce.size();
+    out.keep.assign(E, 0);
+    out.triangles.assign(E, 0);
+    out.goodTriangles.assign(E, 0);
+    Engine::check(pgi_cycle_filter(engine->get(), ce.data(), (uint32_t)E, (uint32_t)numViews, params, out.keep.data(), out.triangles.data(),
+                                   out.goodTriangles.data(), &out.summary));
+    return out;
+}
+
+PoseGraphBuilder::CycleFilterResult PoseGraphBuilder::filterEdgesByCycles(const pgi_edge* d_edges, const std::vector<uint32_t>& src,
+                                                                          const std::vector<uint32_t>& dst, size_t numViews,
+                                                                          const pgi_cycle_params* params, pgi_edge* d_edges_out) {
+    if (src.size() != dst.size()) throw std::invalid_argument("filterEdgesByCycles: inconsistent table sizes");
+    CycleFilterResult out;
+    const size_t P = src.size();
+    out.keep.assign(P, 0);
+    out.triangles.assign(P, 0);
+    out.goodTriangles.assign(P, 0);
+    DevBuf keep(P), tri(P * 4), good(P * 4);
+    Engine::check(pgi_cycle_filter_edges(engine->get(), d_edges, src.data(), dst.data(), (uint32_t)P, (uint32_t)numViews, params,
+                                         keep.as<uint8_t>(), tri.as<uint32_t>(), good.as<uint32_t>(), &out.summary, d_edges_out));
+    if (P && (hipMemcpy(out.keep.data(), keep.p, P, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(out.triangles.data(), tri.p, P * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(out.goodTriangles.data(), good.p, P * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        throw PgiError("filterEdgesByCycles: copying the results back failed");
+    return out;
+}
+
 PoseGraphBuilder::RunStatistics PoseGraphBuilder::run(std::vector<ViewPair>& cand, PoseGraph& poseGraph_, size_t waveSize,
                                                       const SimilarityTable* similarityTable, uint64_t seedBase) {
     RunStatistics st;

@@ -803,6 +803,22 @@ class PoseGraphBuilder {  // include/pose_graph_builder.h:25-171
                                         const std::vector<uint32_t>* rows, size_t numViews, const GlobalRotations& rotations_,
                                         const pgi_transavg_params* transavgParams = nullptr);
 
+    // Cycle-consistency filter (include/pgi.h: pgi_cycle_filter; specification tests/cycle_spec.py): loop closure over the
+    // triangles of the view graph, to be run before the averaging.  One entry per edge, in the order the edges were given.
+    struct CycleFilterResult {
+        std::vector<uint8_t> keep;
+        std::vector<uint32_t> triangles, goodTriangles;
+        pgi_cycle_summary summary{};
+    };
+    // The edges already in a pose graph, in insertion order (the graph is not changed: the caller removes or skips the
+    // edges whose keep byte is 0).
+    CycleFilterResult filterEdgesByCycles(const PoseGraph& poseGraph_, size_t numViews, const pgi_cycle_params* params = nullptr);
+    // The same on a device-resident edge table: pair p = (src[p], dst[p]) with record d_edges[p].  d_edges_out (optional;
+    // may be d_edges itself) receives the table with PGI_EDGE_INCONSISTENT on the dropped records -- what averageTranslations
+    // and pgi_rotation_average_edges take next.
+    CycleFilterResult filterEdgesByCycles(const pgi_edge* d_edges, const std::vector<uint32_t>& src, const std::vector<uint32_t>& dst,
+                                          size_t numViews, const pgi_cycle_params* params = nullptr, pgi_edge* d_edges_out = nullptr);
+
     // Sparse 3-D points of multi-view tracks from the global poses (include/pgi.h: pgi_triangulate_tracks; specification
     // tests/triangulate_spec.py): N-view midpoint, Gauss-Newton on the reprojection error, greedy trimming, parallax test.
     struct TriangulatedPoints {

@@ -8,6 +8,7 @@ from ._lib import EDGE_DTYPE, PgiError, default_params  # noqa: F401
 from ._lib import (TRI_BEHIND, TRI_DEGENERATE, TRI_LOW_PARALLAX, TRI_OK, TRI_REPROJ, TRI_STATUS_COUNT,  # noqa: F401
                    TRI_STATUS_NAMES, TRI_TOO_FEW)
 from ._lib import BA_STOP_EMPTY, BA_STOP_FTOL, BA_STOP_ITERS, BA_STOP_LAMBDA, BundleParams, BundleReport  # noqa: F401
+from ._lib import EDGE_INCONSISTENT, EDGE_OK, CycleParams, CycleSummary  # noqa: F401
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily

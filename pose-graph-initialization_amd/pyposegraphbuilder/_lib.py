@@ -68,6 +68,26 @@ class BundleReport(C.Structure):
                 ("cost_initial", C.c_double), ("cost_final", C.c_double), ("lambda_final", C.c_double)]
 
 
+class CycleParams(C.Structure):
+    """pgi_cycle_params (include/pgi.h)."""
+    _fields_ = [("rot_thr_deg", C.c_double), ("trn_thr_deg", C.c_double), ("collinear_thr_deg", C.c_double),
+                ("min_good", C.c_uint32), ("keep_untested", C.c_uint32)]
+
+
+class CycleSummary(C.Structure):
+    """pgi_cycle_summary (include/pgi.h)."""
+    _fields_ = [("n_triangles", C.c_uint64), ("n_good", C.c_uint64), ("n_skipped_translation", C.c_uint64),
+                ("n_ok", C.c_uint32), ("n_dropped", C.c_uint32)]
+
+
+class CycleEdge(C.Structure):
+    """pgi_cycle_edge (include/pgi.h)."""
+    _fields_ = [("src", C.c_uint32), ("dst", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+# per-edge status (PGI_EDGE_* of include/pgi.h)
+EDGE_OK, EDGE_FEW_INLIERS, EDGE_NAN, EDGE_FEW_POINTS, EDGE_TOO_MANY_ROWS, EDGE_INCONSISTENT = 1, 0, -1, -2, -3, -4
+
 # why the bundle adjustment stopped (PGI_BA_STOP_* of include/pgi.h)
 BA_STOP_ITERS, BA_STOP_FTOL, BA_STOP_LAMBDA, BA_STOP_EMPTY = range(4)
 
@@ -84,6 +104,8 @@ assert EDGE_DTYPE.itemsize == C.sizeof(Edge) == 200
 TRANS_EDGE_DTYPE = np.dtype([("src", "u4"), ("dst", "u4"), ("dir", "f8", 3), ("weight", "f8")])
 assert ROT_EDGE_DTYPE.itemsize == C.sizeof(RotEdge)
 assert TRANS_EDGE_DTYPE.itemsize == C.sizeof(TransEdge) == 40
+CYCLE_EDGE_DTYPE = np.dtype([("src", "u4"), ("dst", "u4"), ("R", "f8", 9), ("t", "f8", 3)])
+assert CYCLE_EDGE_DTYPE.itemsize == C.sizeof(CycleEdge) == 104
 
 # every symbol include/pgi.h declares
 SYMBOLS = ["pgi_last_error", "pgi_device_count", "pgi_default_params", "pgi_create", "pgi_destroy",
@@ -97,7 +119,8 @@ SYMBOLS = ["pgi_last_error", "pgi_device_count", "pgi_default_params", "pgi_crea
            "pgi_tracklets_info", "pgi_tracklets_track",
            "pgi_default_transavg_params", "pgi_translation_average", "pgi_translation_average_edges",
            "pgi_default_triangulate_params", "pgi_triangulate_tracks", "pgi_tracklets_triangulate",
-           "pgi_default_bundle_params", "pgi_bundle_adjust", "pgi_tracklets_bundle_adjust"]
+           "pgi_default_bundle_params", "pgi_bundle_adjust", "pgi_tracklets_bundle_adjust",
+           "pgi_default_cycle_params", "pgi_cycle_filter", "pgi_cycle_filter_edges"]
 COMM_ID_BYTES = 128
 # pgi_allgatherv_fn: int (*)(void* user, const void* send, uint64 send_bytes, void* recv, const uint64* recv_bytes, uint32 world)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32)
@@ -219,6 +242,12 @@ def load():
                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BundleReport)]
     lib.pgi_bundle_adjust.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + ba_args
     lib.pgi_tracklets_bundle_adjust.argtypes = [C.c_void_p] + ba_args
+    lib.pgi_default_cycle_params.restype = None
+    lib.pgi_default_cycle_params.argtypes = [C.POINTER(CycleParams)]
+    lib.pgi_cycle_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(CycleParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.POINTER(CycleSummary)]
+    lib.pgi_cycle_filter_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(CycleParams),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CycleSummary), C.c_void_p]
     _lib = lib
     return lib
 

@@ -335,6 +335,63 @@ class Engine:
             c.ctypes.data_as(C.c_void_p), C.byref(iters), C.byref(used)))
         return c, iters.value, used.value
 
+    # ---- cycle-consistency edge filter ------------------------------------------------------------
+    def _cycle_params(self, kw):
+        prm = L.CycleParams()
+        self._lib.pgi_default_cycle_params(C.byref(prm))
+        for k, v in kw.items():
+            if not hasattr(prm, k):
+                raise TypeError("unknown parameter %r" % k)
+            setattr(prm, k, v)
+        return prm
+
+    @staticmethod
+    def _cycle_summary(s):
+        return {k: int(getattr(s, k)) for k, _ in L.CycleSummary._fields_}
+
+    def cycle_filter(self, src, dst, R_rel, t, n_views, **params):
+        """Triplet checks over the edges (src, dst, R_dst_src, unit t_dst_src), every edge taking part (pgi_cycle_filter;
+        tests/cycle_spec.py).  -> (keep u8 [E], n_tri u32 [E], n_good u32 [E] as CPU tensors, summary dict)."""
+        E = len(src)
+        edges = np.zeros(E, L.CYCLE_EDGE_DTYPE)
+        edges["src"], edges["dst"] = src, dst
+        edges["R"] = np.asarray(R_rel, np.float64).reshape(E, 9)
+        edges["t"] = np.asarray(t, np.float64).reshape(E, 3)
+        prm = self._cycle_params(params)
+        keep, n_tri, n_good = np.zeros(E, np.uint8), np.zeros(E, np.uint32), np.zeros(E, np.uint32)
+        summary = L.CycleSummary()
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if E else None
+        self._bind_stream()
+        L.check(self._lib.pgi_cycle_filter(self._ctx, p(edges), E, n_views, C.byref(prm), p(keep), p(n_tri), p(n_good),
+                                           C.byref(summary)))
+        return (torch.from_numpy(keep), torch.from_numpy(n_tri.view(np.int32)), torch.from_numpy(n_good.view(np.int32)),
+                self._cycle_summary(summary))
+
+    def cycle_filter_edges(self, edges, src, dst, n_views, out=None, **params):
+        """The same on the device-resident edge table (uint8 [P, 200], e.g. the output of allgather_edges): records whose
+        status is not EDGE_OK take no part.  out: None = no table is written; `edges` itself = in place; another uint8
+        [P, 200] device tensor = receives the table with EDGE_INCONSISTENT on the OK records that were not kept.
+        -> (keep u8 [P], n_tri i32 [P], n_good i32 [P] as device tensors, summary dict)"""
+        P = int(edges.shape[0])
+        src = np.ascontiguousarray(src, np.uint32)
+        dst = np.ascontiguousarray(dst, np.uint32)
+        if len(src) != P or len(dst) != P:
+            raise ValueError("src and dst must have one entry per record")
+        if out is not None and (out.dtype != torch.uint8 or out.numel() != P * L.EDGE_DTYPE.itemsize or not out.is_contiguous()
+                                or out.device != edges.device):
+            raise ValueError("out must be a contiguous uint8 [P, 200] tensor on the table's device")
+        prm = self._cycle_params(params)
+        keep = torch.zeros(P, dtype=torch.uint8, device=self.device)
+        n_tri = torch.zeros(P, dtype=torch.int32, device=self.device)
+        n_good = torch.zeros(P, dtype=torch.int32, device=self.device)
+        summary = L.CycleSummary()
+        self._bind_stream()
+        L.check(self._lib.pgi_cycle_filter_edges(
+            self._ctx, _ptr(edges) if P else None, src.ctypes.data_as(C.c_void_p) if P else None,
+            dst.ctypes.data_as(C.c_void_p) if P else None, P, n_views, C.byref(prm), _ptr(keep), _ptr(n_tri), _ptr(n_good),
+            C.byref(summary), _ptr(out) if P else None))
+        return keep, n_tri, n_good, self._cycle_summary(summary)
+
     # ---- triangulation of tracks ------------------------------------------------------------------
     def _triangulate_args(self, keypoints, R, c, has_pose, kw):
         """-> (view array, R, c, has_pose, n_views, params): the host arguments pgi_triangulate_tracks and
