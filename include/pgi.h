@@ -632,6 +632,33 @@ int pgi_tracklets_bundle_adjust(pgi_tracklets* trk, const pgi_keypoint_view* h_v
                                 const uint8_t* h_has_pose, const uint8_t* h_fixed, uint32_t n_views,
                                 const pgi_bundle_params* prm, double* d_X, const uint8_t* d_status,
                                 const uint8_t* d_obs_state, pgi_bundle_report* report);
+/* The same refinement with one more unknown per view: its focal scale phi (specification tests/bundle_focal_spec.py,
+ * DESIGN.md section 3, item 11).  The model uses fx = fx0 * phi and fy = fy0 * phi, fx0 / fy0 being the values of
+ * h_views; cx and cy are not refined.  d r / d phi = (fx0 a, fy0 b), the update is phi <- phi + dphi, and a trial point
+ * at which some phi > 0 fails (a NaN fails it) is rejected like one with a non-positive depth.  A view is FOCAL-FREE
+ * when it has a pose, is not marked in h_focal_fixed and has at least min_focal_obs participating observations (0 is
+ * taken as 1; the Python default of 30 is a choice, not a measurement).  This does not depend on its pose being free:
+ * the gauge view and an h_fixed view may have a free focal, a free view may have a held one.  The camera block grows
+ * from 6 x 6 to 7 x 7; participation, gauge, Huber weights, damping, gain ratio and stopping rules are unchanged, and
+ * pgi_bundle_report keeps its meaning (n_free_cams counts the pose-free views).  A call that ends with no focal-free
+ * view runs the six-parameter kernels on fx0 * phi, fy0 * phi and returns the bits pgi_bundle_adjust returns for views
+ * scaled that way by the caller.
+ * h_focal: n_views, in-out, phi at the start and on return; only focal-free views change.  h_focal_fixed: n_views bytes
+ * or NULL.  n_free_focals: optional.  The caller multiplies fx, fy by the returned phi before it triangulates again; the
+ * library does not.  PGI_ERR_INVALID (nothing is written): h_focal == NULL, a non-finite or non-positive phi of a view
+ * that has a pose, and whatever pgi_bundle_adjust refuses. */
+int pgi_bundle_adjust_focal(pgi_ctx* ctx, const uint32_t* d_track_begin, const uint64_t* d_members, uint32_t n_tracks,
+                            const pgi_keypoint_view* h_views, double* h_R, double* h_c, const uint8_t* h_has_pose,
+                            const uint8_t* h_fixed, uint32_t n_views, const pgi_bundle_params* prm, double* d_X,
+                            const uint8_t* d_status, const uint8_t* d_obs_state, double* h_focal,
+                            const uint8_t* h_focal_fixed, uint32_t min_focal_obs, pgi_bundle_report* report,
+                            uint32_t* n_free_focals);
+/* The same on the store's current by-track ordering, mirroring pgi_tracklets_bundle_adjust. */
+int pgi_tracklets_bundle_adjust_focal(pgi_tracklets* trk, const pgi_keypoint_view* h_views, double* h_R, double* h_c,
+                                      const uint8_t* h_has_pose, const uint8_t* h_fixed, uint32_t n_views,
+                                      const pgi_bundle_params* prm, double* d_X, const uint8_t* d_status,
+                                      const uint8_t* d_obs_state, double* h_focal, const uint8_t* h_focal_fixed,
+                                      uint32_t min_focal_obs, pgi_bundle_report* report, uint32_t* n_free_focals);
 
 #ifdef __cplusplus
 }

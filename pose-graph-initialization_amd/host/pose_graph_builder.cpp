@@ -1894,25 +1894,41 @@ PoseGraphBuilder::TriangulatedPoints PoseGraphBuilder::triangulateTracks(const T
     return triangulateTracks(begin, members, views, rotations_, positions_, hasPose, params);
 }
 
-PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjust(const std::vector<uint32_t>& trackBegin, const std::vector<uint64_t>& members,
-                                                                  const std::vector<ViewFeaturesRef>& views,
-                                                                  const GlobalRotations& rotations_, const GlobalPositions& positions_,
-                                                                  const TriangulatedPoints& points_, const std::vector<uint8_t>* hasPose,
-                                                                  const std::vector<uint8_t>* fixed, const pgi_bundle_params* params) {
-    BundleAdjustment out;
+namespace {
+struct FocalArguments {  // what bundleAdjustFocal adds to bundleAdjust
+    const std::vector<double>* scales;
+    const std::vector<uint8_t>* fixed;
+    uint32_t minObs;
+};
+}  // namespace
+
+// the body bundleAdjust and bundleAdjustFocal share (focal == nullptr: pgi_bundle_adjust)
+static PoseGraphBuilder::BundleAdjustment bundleAdjustBody(pgi_ctx* ctx, const char* who, const std::vector<uint32_t>& trackBegin,
+                                                           const std::vector<uint64_t>& members,
+                                                           const std::vector<PoseGraphBuilder::ViewFeaturesRef>& views,
+                                                           const PoseGraphBuilder::GlobalRotations& rotations_,
+                                                           const PoseGraphBuilder::GlobalPositions& positions_,
+                                                           const PoseGraphBuilder::TriangulatedPoints& points_,
+                                                           const std::vector<uint8_t>* hasPose, const std::vector<uint8_t>* fixed,
+                                                           const pgi_bundle_params* params, const FocalArguments* focal) {
+    PoseGraphBuilder::BundleAdjustment out;
     out.rotations = rotations_;
     out.positions = positions_;
     out.points = points_.points;
     out.report.stop_reason = PGI_BA_STOP_EMPTY;
     const size_t V = views.size(), T = trackBegin.empty() ? 0 : trackBegin.size() - 1, M = members.size();
     if (rotations_.rotations.size() != V || positions_.positions.size() != V)
-        throw std::invalid_argument("bundleAdjust: one global rotation and one position per view are needed");
-    if ((hasPose && hasPose->size() != V) || (fixed && fixed->size() != V)) throw std::invalid_argument("bundleAdjust: one flag per view is needed");
-    if (T && trackBegin.back() != M) throw std::invalid_argument("bundleAdjust: the last offset must be the member count");
+        throw std::invalid_argument(std::string(who) + ": one global rotation and one position per view are needed");
+    if ((hasPose && hasPose->size() != V) || (fixed && fixed->size() != V)) throw std::invalid_argument(std::string(who) + ": one flag per view is needed");
+    if (T && trackBegin.back() != M) throw std::invalid_argument(std::string(who) + ": the last offset must be the member count");
     if (points_.points.size() != T || points_.status.size() != T || points_.observationState.size() != M)
-        throw std::invalid_argument("bundleAdjust: points, status and observation states must match the tracks");
+        throw std::invalid_argument(std::string(who) + ": points, status and observation states must match the tracks");
+    if (focal) {
+        if (focal->scales->size() != V || (focal->fixed && focal->fixed->size() != V))
+            throw std::invalid_argument(std::string(who) + ": one focal scale and one flag per view are needed");
+        out.focalScales = *focal->scales;
+    }
     if (!T || !V) return out;
-    pgi_ctx* ctx = engine->get();
     HIP_OK(hipSetDevice(engineDevice(ctx)));
     struct Block {  // one device block: keypoints, offsets, members, points, status, states
         void* p = nullptr;
@@ -1931,7 +1947,7 @@ PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjust(const std::vec
     for (size_t v = 0; v < V; ++v) {
         const size_t n = views[v].size();
         if (n) {
-            if (!views[v].keypoints) throw PgiError("bundleAdjust: null keypoint array");
+            if (!views[v].keypoints) throw PgiError(std::string(who) + ": null keypoint array");
             HIP_OK(hipMemcpyAsync(d + kpOff[v], views[v].keypoints, n * 8, hipMemcpyHostToDevice, s));
         }
         kv[v] = pgi_keypoint_view{n ? (const float*)(d + kpOff[v]) : nullptr, (uint32_t)n, 0, views[v].focalLength, views[v].focalLength,
@@ -1944,9 +1960,16 @@ PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjust(const std::vec
     HIP_OK(hipMemcpyAsync(d + oX, points_.points[0].data(), T * 24, hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(d + oStatus, points_.status.data(), T, hipMemcpyHostToDevice, s));
     if (M) HIP_OK(hipMemcpyAsync(d + oState, points_.observationState.data(), M, hipMemcpyHostToDevice, s));
-    Engine::check(pgi_bundle_adjust(ctx, (const uint32_t*)(d + oBegin), (const uint64_t*)(d + oMem), (uint32_t)T, kv.data(), R.data(), c.data(),
-                                    hasPose ? hasPose->data() : nullptr, fixed ? fixed->data() : nullptr, (uint32_t)V, params,
-                                    (double*)(d + oX), (const uint8_t*)(d + oStatus), (const uint8_t*)(d + oState), &out.report));
+    if (focal)
+        Engine::check(pgi_bundle_adjust_focal(ctx, (const uint32_t*)(d + oBegin), (const uint64_t*)(d + oMem), (uint32_t)T, kv.data(), R.data(),
+                                              c.data(), hasPose ? hasPose->data() : nullptr, fixed ? fixed->data() : nullptr, (uint32_t)V, params,
+                                              (double*)(d + oX), (const uint8_t*)(d + oStatus), (const uint8_t*)(d + oState),
+                                              out.focalScales.data(), focal->fixed ? focal->fixed->data() : nullptr, focal->minObs,
+                                              &out.report, &out.freeFocals));
+    else
+        Engine::check(pgi_bundle_adjust(ctx, (const uint32_t*)(d + oBegin), (const uint64_t*)(d + oMem), (uint32_t)T, kv.data(), R.data(), c.data(),
+                                        hasPose ? hasPose->data() : nullptr, fixed ? fixed->data() : nullptr, (uint32_t)V, params,
+                                        (double*)(d + oX), (const uint8_t*)(d + oStatus), (const uint8_t*)(d + oState), &out.report));
     HIP_OK(hipMemcpyAsync(out.points[0].data(), d + oX, T * 24, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     for (size_t v = 0; v < V; ++v) {
@@ -1954,6 +1977,42 @@ PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjust(const std::vec
         std::memcpy(out.positions.positions[v].data(), &c[v * 3], 24);
     }
     return out;
+}
+
+PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjust(const std::vector<uint32_t>& trackBegin, const std::vector<uint64_t>& members,
+                                                                  const std::vector<ViewFeaturesRef>& views,
+                                                                  const GlobalRotations& rotations_, const GlobalPositions& positions_,
+                                                                  const TriangulatedPoints& points_, const std::vector<uint8_t>* hasPose,
+                                                                  const std::vector<uint8_t>* fixed, const pgi_bundle_params* params) {
+    return bundleAdjustBody(engine->get(), "bundleAdjust", trackBegin, members, views, rotations_, positions_, points_, hasPose, fixed, params,
+                            nullptr);
+}
+
+PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjustFocal(const std::vector<uint32_t>& trackBegin, const std::vector<uint64_t>& members,
+                                                                       const std::vector<ViewFeaturesRef>& views,
+                                                                       const GlobalRotations& rotations_, const GlobalPositions& positions_,
+                                                                       const TriangulatedPoints& points_, const std::vector<double>& focalScales,
+                                                                       const std::vector<uint8_t>* hasPose, const std::vector<uint8_t>* fixed,
+                                                                       const std::vector<uint8_t>* focalFixed, uint32_t minFocalObs,
+                                                                       const pgi_bundle_params* params) {
+    const FocalArguments focal{&focalScales, focalFixed, minFocalObs};
+    return bundleAdjustBody(engine->get(), "bundleAdjustFocal", trackBegin, members, views, rotations_, positions_, points_, hasPose, fixed,
+                            params, &focal);
+}
+
+PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjustFocal(const Tracklets& tracks_, const std::vector<ViewFeaturesRef>& views,
+                                                                       const GlobalRotations& rotations_, const GlobalPositions& positions_,
+                                                                       const TriangulatedPoints& points_, const std::vector<double>& focalScales,
+                                                                       const std::vector<uint8_t>* hasPose, const std::vector<uint8_t>* fixed,
+                                                                       const std::vector<uint8_t>* focalFixed, uint32_t minFocalObs,
+                                                                       const pgi_bundle_params* params) {
+    std::vector<uint32_t> begin(1, 0);
+    std::vector<uint64_t> members;
+    for (size_t t = 0; t < tracks_.trackNumber(); ++t) {
+        for (const Tracklets::Pair& m : tracks_.track(t)) members.push_back(((uint64_t)m.first << 32) | (uint64_t)(uint32_t)m.second);
+        begin.push_back((uint32_t)members.size());
+    }
+    return bundleAdjustFocal(begin, members, views, rotations_, positions_, points_, focalScales, hasPose, fixed, focalFixed, minFocalObs, params);
 }
 
 PoseGraphBuilder::BundleAdjustment PoseGraphBuilder::bundleAdjust(const Tracklets& tracks_, const std::vector<ViewFeaturesRef>& views,

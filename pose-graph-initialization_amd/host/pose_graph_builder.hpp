@@ -851,6 +851,8 @@ class PoseGraphBuilder {  // include/pose_graph_builder.h:25-171
         GlobalPositions positions;
         std::vector<Vector3d> points;  // refined where the track took part
         pgi_bundle_report report{};
+        std::vector<double> focalScales;  // bundleAdjustFocal: phi per view, refined where the view was focal-free
+        uint32_t freeFocals = 0;          // bundleAdjustFocal: focal-free views
     };
     BundleAdjustment bundleAdjust(const std::vector<uint32_t>& trackBegin, const std::vector<uint64_t>& members,
                                   const std::vector<ViewFeaturesRef>& views, const GlobalRotations& rotations_,
@@ -862,6 +864,23 @@ class PoseGraphBuilder {  // include/pose_graph_builder.h:25-171
                                   const GlobalRotations& rotations_, const GlobalPositions& positions_,
                                   const TriangulatedPoints& points_, const std::vector<uint8_t>* hasPose = nullptr,
                                   const std::vector<uint8_t>* fixed = nullptr, const pgi_bundle_params* params = nullptr);
+    // The same with one focal scale per view among the unknowns (include/pgi.h: pgi_bundle_adjust_focal; specification
+    // tests/bundle_focal_spec.py): fx = fy = focalLength * phi.  focalScales: phi at the start, one per view.  A view's focal
+    // is free when it has a pose, is not marked in focalFixed and has at least minFocalObs participating observations (30 is
+    // a choice, not a measurement).  The caller multiplies the focal lengths by the returned focalScales before it
+    // triangulates again.
+    BundleAdjustment bundleAdjustFocal(const std::vector<uint32_t>& trackBegin, const std::vector<uint64_t>& members,
+                                       const std::vector<ViewFeaturesRef>& views, const GlobalRotations& rotations_,
+                                       const GlobalPositions& positions_, const TriangulatedPoints& points_,
+                                       const std::vector<double>& focalScales, const std::vector<uint8_t>* hasPose = nullptr,
+                                       const std::vector<uint8_t>* fixed = nullptr, const std::vector<uint8_t>* focalFixed = nullptr,
+                                       uint32_t minFocalObs = 30, const pgi_bundle_params* params = nullptr);
+    BundleAdjustment bundleAdjustFocal(const class Tracklets& tracks_, const std::vector<ViewFeaturesRef>& views,
+                                       const GlobalRotations& rotations_, const GlobalPositions& positions_,
+                                       const TriangulatedPoints& points_, const std::vector<double>& focalScales,
+                                       const std::vector<uint8_t>* hasPose = nullptr, const std::vector<uint8_t>* fixed = nullptr,
+                                       const std::vector<uint8_t>* focalFixed = nullptr, uint32_t minFocalObs = 30,
+                                       const pgi_bundle_params* params = nullptr);
 
     struct RunStatistics {  // the reference's RunningStatistics keys that concern this path (utils.h:15-73)
         size_t pairsProcessed = 0, edgesAdded = 0, pathsSearched = 0, pathsFound = 0, touchedNodes = 0,

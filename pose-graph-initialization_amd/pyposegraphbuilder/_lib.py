@@ -120,6 +120,7 @@ SYMBOLS = ["pgi_last_error", "pgi_device_count", "pgi_default_params", "pgi_crea
            "pgi_default_transavg_params", "pgi_translation_average", "pgi_translation_average_edges",
            "pgi_default_triangulate_params", "pgi_triangulate_tracks", "pgi_tracklets_triangulate",
            "pgi_default_bundle_params", "pgi_bundle_adjust", "pgi_tracklets_bundle_adjust",
+           "pgi_bundle_adjust_focal", "pgi_tracklets_bundle_adjust_focal",
            "pgi_default_cycle_params", "pgi_cycle_filter", "pgi_cycle_filter_edges"]
 COMM_ID_BYTES = 128
 # pgi_allgatherv_fn: int (*)(void* user, const void* send, uint64 send_bytes, void* recv, const uint64* recv_bytes, uint32 world)
@@ -242,6 +243,10 @@ def load():
                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BundleReport)]
     lib.pgi_bundle_adjust.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + ba_args
     lib.pgi_tracklets_bundle_adjust.argtypes = [C.c_void_p] + ba_args
+    # ... d_obs_state, h_focal, h_focal_fixed, min_focal_obs, report, n_free_focals
+    baf_args = ba_args[:-1] + [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(BundleReport), C.POINTER(C.c_uint32)]
+    lib.pgi_bundle_adjust_focal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + baf_args
+    lib.pgi_tracklets_bundle_adjust_focal.argtypes = [C.c_void_p] + baf_args
     lib.pgi_default_cycle_params.restype = None
     lib.pgi_default_cycle_params.argtypes = [C.POINTER(CycleParams)]
     lib.pgi_cycle_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(CycleParams), C.c_void_p, C.c_void_p,

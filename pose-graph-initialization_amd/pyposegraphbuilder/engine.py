@@ -35,12 +35,14 @@ class BundleResult:
     """Result of Engine.bundle_adjust / DeviceTracklets.bundle_adjust: R [V,3,3] and c [V,3] (numpy, refined where the view
     was free), X [T,3] f64 (device tensor, refined where the track took part) and the fields of pgi_bundle_report: iters,
     accepted, cg_iters_total, stop_reason (pyposegraphbuilder.BA_STOP_*), n_obs, n_points, n_free_cams, cost_initial,
-    cost_final, lambda_final."""
+    cost_final, lambda_final.  With refine_focal: focal [V] (the focal scales phi, refined where the view was focal-free)
+    and n_free_focals; both None otherwise."""
     FIELDS = ("iters", "accepted", "cg_iters_total", "stop_reason", "n_obs", "n_points", "n_free_cams", "cost_initial",
               "cost_final", "lambda_final")
 
-    def __init__(self, R, c, X, report):
+    def __init__(self, R, c, X, report, focal=None, n_free_focals=None):
         self.R, self.c, self.X = R, c, X
+        self.focal, self.n_free_focals = focal, n_free_focals
         for k in self.FIELDS:
             setattr(self, k, getattr(report, k))
 
@@ -478,11 +480,33 @@ class Engine:
                 _ptr(ob) if M else None, C.byref(rep))
         return args, (Rh.reshape(V, 3, 3), ch.reshape(V, 3), Xd, rep), (views, hp, fx, st, ob, prm)
 
-    def bundle_adjust(self, track_begin, members, keypoints, R, c, X, status, obs_state, has_pose=None, fixed=None, **params):
+    @staticmethod
+    def _focal_keywords(refine_focal, focal, focal_fixed):
+        """focal / focal_fixed without refine_focal would be ignored and the result a pose-only one at unscaled focals."""
+        if not refine_focal and (focal is not None or focal_fixed is not None):
+            raise ValueError("focal and focal_fixed need refine_focal=True")
+
+    @staticmethod
+    def _focal_args(args, V, focal, focal_fixed, min_focal_obs):
+        """The shared arguments extended to those of the *_focal entries -> (args, phi [V] (a copy), n_free_focals, keep)."""
+        phi = np.ones(V, np.float64) if focal is None else np.array(focal, np.float64).reshape(-1)
+        ff = None if focal_fixed is None else np.ascontiguousarray(np.asarray(focal_fixed) != 0, np.uint8)
+        if phi.size != V or (ff is not None and ff.size != V):
+            raise ValueError("focal and focal_fixed must have one entry per view")
+        n = C.c_uint32(0)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        return args[:-1] + (ptr(phi), ptr(ff), int(min_focal_obs), args[-1], C.byref(n)), phi, n, (ff,)
+
+    def bundle_adjust(self, track_begin, members, keypoints, R, c, X, status, obs_state, has_pose=None, fixed=None, focal=None,
+                      focal_fixed=None, min_focal_obs=30, refine_focal=False, **params):
         """Joint refinement of poses and points (pgi_bundle_adjust; specification tests/bundle_spec.py).  Tracks, keypoints,
         R, c and has_pose as in triangulate_tracks; X, status and obs_state as it returned them (arrays or device tensors);
         fixed [V] or None = the first posed view with observations holds the gauge.  params: iters, cg_iters, min_cam_obs,
-        use_low_parallax, huber_px, cg_tol, ftol, lambda_init.  The inputs are not modified.  -> BundleResult."""
+        use_low_parallax, huber_px, cg_tol, ftol, lambda_init.  The inputs are not modified.  -> BundleResult.
+        refine_focal=True (pgi_bundle_adjust_focal; specification tests/bundle_focal_spec.py): each view's focal scale phi
+        (focal [V], None = 1) joins the unknowns where the view is posed, not marked in focal_fixed and has at least
+        min_focal_obs participating observations (30 is a choice, not a measurement); the result carries focal and
+        n_free_focals.  The caller multiplies fx, fy by the returned focal before triangulating again."""
         dev = self.device
         tb = track_begin.to(dev) if torch.is_tensor(track_begin) else torch.from_numpy(np.array(track_begin, np.uint32).view(np.int32)).to(dev)
         mem = members.to(dev) if torch.is_tensor(members) else torch.from_numpy(np.array(members, np.uint64).view(np.int64)).to(dev)
@@ -491,6 +515,11 @@ class Engine:
         T, M = max(int(tb.numel()) - 1, 0), int(mem.numel())
         args, (Rh, ch, Xd, rep), keep = self._bundle_args(keypoints, R, c, X, status, obs_state, has_pose, fixed, T, M, params)
         self._bind_stream()
+        self._focal_keywords(refine_focal, focal, focal_fixed)
+        if refine_focal:
+            args, phi, n, keep2 = self._focal_args(args, len(Rh), focal, focal_fixed, min_focal_obs)
+            L.check(self._lib.pgi_bundle_adjust_focal(self._ctx, _ptr(tb) if T else None, _ptr(mem) if M else None, T, *args))
+            return BundleResult(Rh, ch, Xd, rep, phi, n.value)
         L.check(self._lib.pgi_bundle_adjust(self._ctx, _ptr(tb) if T else None, _ptr(mem) if M else None, T, *args))
         return BundleResult(Rh, ch, Xd, rep)
 
@@ -726,13 +755,20 @@ class DeviceTracklets:
             _ptr(st) if M else None, counts.ctypes.data_as(C.c_void_p)))
         return Triangulation(X, status, err, nu, st, counts)
 
-    def bundle_adjust(self, keypoints, R, c, X, status, obs_state, has_pose=None, fixed=None, **params):
-        """Engine.bundle_adjust on the store's current by-track ordering (pgi_tracklets_bundle_adjust), e.g. with the X,
-        status and obs_state of triangulate(); no member leaves the device.  -> BundleResult."""
+    def bundle_adjust(self, keypoints, R, c, X, status, obs_state, has_pose=None, fixed=None, focal=None, focal_fixed=None,
+                      min_focal_obs=30, refine_focal=False, **params):
+        """Engine.bundle_adjust on the store's current by-track ordering (pgi_tracklets_bundle_adjust, or
+        pgi_tracklets_bundle_adjust_focal with refine_focal), e.g. with the X, status and obs_state of triangulate(); no
+        member leaves the device.  -> BundleResult."""
         eng = self.eng
         i = self.info()
         args, (Rh, ch, Xd, rep), keep = eng._bundle_args(keypoints, R, c, X, status, obs_state, has_pose, fixed, i["tracks"], i["events"], params)
         eng._bind_stream()
+        eng._focal_keywords(refine_focal, focal, focal_fixed)
+        if refine_focal:
+            args, phi, n, keep2 = eng._focal_args(args, len(Rh), focal, focal_fixed, min_focal_obs)
+            L.check(self._lib.pgi_tracklets_bundle_adjust_focal(self._t, *args))
+            return BundleResult(Rh, ch, Xd, rep, phi, n.value)
         L.check(self._lib.pgi_tracklets_bundle_adjust(self._t, *args))
         return BundleResult(Rh, ch, Xd, rep)
 
