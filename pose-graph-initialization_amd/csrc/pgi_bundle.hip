@@ -33,6 +33,7 @@
 // after the sums, so that they hold lambda D alone and their PCG components stay exactly 0.  A per-view table (fx0, fy0, phi)
 // is saved and restored with the view table.  A call with no focal-free view runs the NC = 6 kernels on the scaled table.
 #include "pgi_internal.hpp"
+#include "pgi_reduce.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -80,28 +81,6 @@ struct BaCgState {
     int done;
 };
 
-BDEV double ba_wave_sum(double v) {  // xor tree: the same shape on every call, the sum in every lane
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-// sum over the 256 threads in a fixed tree order, valid in thread 0
-BDEV double ba_block_sum(double v, double* red, int tid) {
-    red[tid] = v;
-    __syncthreads();
-    for (int s = kBaBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-BDEV double ba_reduce_partials(const double* __restrict__ part, uint32_t n, int lane) {
-    double s = 0.0;
-    for (uint32_t b = (uint32_t)lane; b < n; b += kBaWave) s += part[b];
-    return ba_wave_sum(s);
-}
 // inverse of a symmetric 3 x 3 matrix (00 01 02 11 12 22) by its adjugate, the operation order of tri_solve_sym3
 BDEV void ba_inv_sym3(const double* a, double* inv) {
     const double c00 = a[3] * a[5] - a[4] * a[4];
@@ -310,10 +289,10 @@ __global__ __launch_bounds__(kBaBlock) void ba_eval_kernel(BaEval A) {
             pred = wt * ((r0 * r0 + r1 * r1) - (l0 * l0 + l1 * l1));
         }
     }
-    const double c = ba_block_sum(rho, red, tid);
+    const double c = block_tree_sum<kBaBlock>(rho, red, tid);
     if (tid == 0) A.part_cost[blockIdx.x] = c;
     if (TRIAL) {
-        const double p = ba_block_sum(pred, red, tid);
+        const double p = block_tree_sum<kBaBlock>(pred, red, tid);
         if (tid == 0) A.part_pred[blockIdx.x] = p;
     }
 }
@@ -324,7 +303,7 @@ __global__ __launch_bounds__(kBaBlock) void ba_reduce_kernel(const double* __res
     const double* p = part + (size_t)blockIdx.x * stride;
     double s = 0.0;
     for (uint32_t b = (uint32_t)tid; b < n; b += kBaBlock) s += p[b];
-    s = ba_block_sum(s, red, tid);
+    s = block_tree_sum<kBaBlock>(s, red, tid);
     if (tid == 0) out[blockIdx.x] = s;
 }
 
@@ -471,9 +450,9 @@ __global__ __launch_bounds__(kBaBlock) void ba_cam_setup_kernel(BaCam A, const d
         }
     }
 #pragma unroll
-    for (int i = 0; i < NT; ++i) S[i] = ba_wave_sum(S[i]);
+    for (int i = 0; i < NT; ++i) S[i] = wave_sum(S[i]);
 #pragma unroll
-    for (int i = 0; i < NC; ++i) dU[i] = ba_wave_sum(dU[i]), b[i] = ba_wave_sum(b[i]);
+    for (int i = 0; i < NC; ++i) dU[i] = wave_sum(dU[i]), b[i] = wave_sum(b[i]);
     if (lane != 0) return;
     double L[NT], z[NC], ld[NC];
 #pragma unroll
@@ -568,7 +547,7 @@ __global__ __launch_bounds__(kBaBlock) void ba_cam_pass_kernel(BaCam A, const do
         }
     }
 #pragma unroll
-    for (int i = 0; i < NC; ++i) acc[i] = ba_wave_sum(acc[i]);
+    for (int i = 0; i < NC; ++i) acc[i] = wave_sum(acc[i]);
     if (lane != 0) return;
     double pq = 0.0;
 #pragma unroll
@@ -595,7 +574,7 @@ __global__ __launch_bounds__(kBaWave) void ba_cg_dir_kernel(uint32_t n_views, co
         if (blockIdx.x == 0 && lane == 0) *st_next = sp;
         return;
     }
-    const double rz = ba_reduce_partials(part_rz, n_views, lane);
+    const double rz = wave_sum(strided_sum<kBaWave>(part_rz, n_views, 1, lane));
     const double rz0 = first ? rz : sp.rz0;
     const double beta = (!first && sp.rz > 0.0) ? rz / sp.rz : 0.0;
     const bool done = !(rz > (tol * tol) * rz0) || sp.iters >= cap;
@@ -614,7 +593,7 @@ __global__ __launch_bounds__(kBaWave) void ba_cg_update_kernel(uint32_t n_views,
     const BaCgState s = *st;
     if (s.done) return;  // (uniform)
     const int lane = threadIdx.x;
-    const double pq = ba_reduce_partials(part_pq, n_views, lane);
+    const double pq = wave_sum(strided_sum<kBaWave>(part_pq, n_views, 1, lane));
     const double alpha = pq > 0.0 ? s.rz / pq : 0.0;
     const uint32_t v = blockIdx.x * kBaWave + (uint32_t)lane;
     if (v >= n_views) return;

@@ -1,9 +1,12 @@
 // pgi_internal.hpp -- shared by the translation units of libpgi.so (not part of the C ABI)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <string>
+#include <vector>
 #include "../../include/pgi.h"
 
 namespace pgi {
@@ -19,6 +22,41 @@ inline int fail(int code, const std::string& msg) {
         if (_e != hipSuccess)                                                                        \
             return pgi::fail(PGI_ERR_DEVICE, std::string(#x) + ": " + hipGetErrorString(_e));        \
     } while (0)
+
+namespace pgi {
+// One device allocation handed out as typed regions, for buffers that live as long as one call.  Declare every region with
+// its element count -- add(p, n) -- then alloc(): one hipMalloc, every region at a 256-byte boundary, the pointers set.  The
+// pointers registered must stay where they are until alloc().  The destructor frees the block.
+class DeviceWorkspace {
+public:
+    DeviceWorkspace() = default;
+    DeviceWorkspace(const DeviceWorkspace&) = delete;
+    DeviceWorkspace& operator=(const DeviceWorkspace&) = delete;
+    ~DeviceWorkspace() { if (base_) (void)hipFree(base_); }
+    template <class T>
+    void add(T*& p, size_t count) {
+        const size_t off = bytes_;
+        bytes_ += (count * sizeof(T) + 255) & ~(size_t)255;
+        bind_.push_back([&p, off](char* base) { p = reinterpret_cast<T*>(base + off); });
+    }
+    hipError_t alloc() {
+        const hipError_t e = hipMalloc((void**)&base_, std::max<size_t>(bytes_, 256));
+        if (e == hipSuccess)
+            for (auto& b : bind_) b(base_);
+        return e;
+    }
+    bool allocated() const { return base_ != nullptr; }
+private:
+    char* base_ = nullptr;
+    size_t bytes_ = 0;
+    std::vector<std::function<void(char*)>> bind_;
+};
+// host vector -> the region declared for it
+template <class T>
+inline hipError_t upload(T* dst, const std::vector<T>& src, hipStream_t st) {
+    return hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, st);
+}
+}  // namespace pgi
 
 struct pgi_ctx {
     int device;

@@ -14,13 +14,17 @@
 //                        view), CG scalars and the convergence flag resident on the device, the host looks after a
 //                        predicted number of launches; deterministic
 //   rot_solve_tree_kernel  sparse, sequence-like graphs (E <= 8 V): spanning-tree preconditioner, on chip
-//   cg2_*_kernel         dense band-like graphs (deep breadth-first walk): two-level preconditioner, Jacobi + a coarse
-//                        space of <= 127 aggregates of neighbouring views, coarse matrix inverted on the device per step
+//   cg_*_kernel<true>,   dense band-like graphs (deep breadth-first walk): two-level preconditioner, Jacobi + a coarse
+//   cg2_coarse_*_kernel  space of <= 127 aggregates of neighbouring views, coarse matrix inverted on the device per step
 //   rot_update_kernel    one thread per view   : R_k <- R_k exp(d_k)
+// Every floating-point sum goes through pgi_reduce.hpp (one documented association each); the host-side graph preparation
+// (incidence CSR, spanning forest, tree order, aggregates) is pgi_graph_host.hpp.
 // Multi-GPU: "replicas only" -- after the all-gather of the edge records every rank (or rank 0)
 // runs this identical solve; an edge-partitioned CG would pay an all-reduce per iteration for a
 // 3V-vector and is pure latency.
 #include "pgi_internal.hpp"
+#include "pgi_graph_host.hpp"
+#include "pgi_reduce.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -30,6 +34,7 @@
 #include <cstddef>
 #include <cstring>
 #include <numeric>
+#include <type_traits>
 #include <vector>
 
 namespace pgi {
@@ -133,26 +138,6 @@ __global__ __launch_bounds__(256) void rot_residual_kernel(const RotEdgeDev* __r
     w[e] = wt;
 }
 
-// block-wide sum of three doubles, fixed tree order (deterministic)
-__device__ void block_sum3(double v[3], double* red /* 3*1024 */, int tid) {
-    red[tid] = v[0];
-    red[1024 + tid] = v[1];
-    red[2048 + tid] = v[2];
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[tid] += red[tid + s];
-            red[1024 + tid] += red[1024 + tid + s];
-            red[2048 + tid] += red[2048 + tid + s];
-        }
-        __syncthreads();
-    }
-    v[0] = red[0];
-    v[1] = red[1024];
-    v[2] = red[2048];
-    __syncthreads();
-}
-
 // adj_ptr[V+1]; adj_edge / adj_other / adj_sign per incidence (sign +1: the vertex is dst, -1: src)
 __global__ __launch_bounds__(1024) void rot_solve_kernel(uint32_t n_views, const uint32_t* __restrict__ adj_ptr,
                                                          const uint32_t* __restrict__ adj_edge,
@@ -191,7 +176,7 @@ __global__ __launch_bounds__(1024) void rot_solve_kernel(uint32_t n_views, const
             rz[c] += b[c] * z;
         }
     }
-    block_sum3(rz, red, tid);
+    block_tree_sum<3, 1024>(rz, red, tid);
     const double rz0[3] = {rz[0], rz[1], rz[2]};
     uint32_t it = 0;
     for (; it < cg_iters; ++it) {
@@ -215,9 +200,7 @@ __global__ __launch_bounds__(1024) void rot_solve_kernel(uint32_t n_views, const
 #pragma unroll
                     for (int c = 0; c < 3; ++c) y[c] -= we * p[3 * (size_t)o + c];
                 }
-            for (uint32_t m = 1; m < row_lanes; m <<= 1)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) y[c] += __shfl_xor(y[c], (int)m);
+            row_lanes_sum<3>(y, row_lanes);
             if (live && sub == 0u) {
                 const double d = diag[k];
 #pragma unroll
@@ -228,7 +211,7 @@ __global__ __launch_bounds__(1024) void rot_solve_kernel(uint32_t n_views, const
                 }
             }
         }
-        block_sum3(pAp, red, tid);
+        block_tree_sum<3, 1024>(pAp, red, tid);
         double alpha[3], rzn[3] = {0, 0, 0};
 #pragma unroll
         for (int c = 0; c < 3; ++c) alpha[c] = pAp[c] > 0.0 ? rz[c] / pAp[c] : 0.0;
@@ -243,7 +226,7 @@ __global__ __launch_bounds__(1024) void rot_solve_kernel(uint32_t n_views, const
                 rzn[c] += rn * (rn * inv);
             }
         }
-        block_sum3(rzn, red, tid);
+        block_tree_sum<3, 1024>(rzn, red, tid);
         for (uint32_t k = tid; k < n_views; k += 1024) {
             const double d = diag[k], inv = d > 0.0 ? 1.0 / d : 0.0;
 #pragma unroll
@@ -261,7 +244,7 @@ __global__ __launch_bounds__(1024) void rot_solve_kernel(uint32_t n_views, const
     for (uint32_t k = tid; k < n_views; k += 1024)
         nd[0] += sqrt(x[3 * (size_t)k] * x[3 * (size_t)k] + x[3 * (size_t)k + 1] * x[3 * (size_t)k + 1] +
                       x[3 * (size_t)k + 2] * x[3 * (size_t)k + 2]);
-    block_sum3(nd, red, tid);
+    block_tree_sum<3, 1024>(nd, red, tid);
     if (tid == 0) {
         stats[0] = nd[0] / (double)n_views;
         stats[1] = (double)it;
@@ -282,39 +265,6 @@ __global__ __launch_bounds__(1024) void rot_solve_kernel(uint32_t n_views, const
 // is a dozen workgroup barriers.  Scans run in a fixed order: same input, same bits.
 constexpr uint32_t kTreeViews = 6144;
 constexpr int kTreeOwn = kTreeViews / 1024;
-
-__device__ inline double wave_sum_fixed(double v) {  // xor tree: the same order on every call
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-// sum over the 1024 threads, returned to all of them; red: 16 doubles of LDS
-__device__ inline double block_sum_1024(double v, double* red, int tid) {
-    v = wave_sum_fixed(v);
-    __syncthreads();  // previous use of red is over
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += red[i];
-    return s;
-}
-// exclusive prefix (in thread order) of one value per thread; red: 16 doubles of LDS
-__device__ inline double block_prefix_1024(double v, double* red, int tid) {
-    const int lane = tid & 63, wv = tid >> 6;
-    double x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    __syncthreads();  // previous use of red is over
-    if (lane == 63) red[wv] = x;
-    __syncthreads();
-    double before = 0.0;
-    for (int i = 0; i < wv; ++i) before += red[i];
-    return before + (x - v);
-}
 
 struct TreeIncidence {  // one 16-byte load per incidence in the products
     double w;
@@ -413,7 +363,7 @@ __global__ __launch_bounds__(1024) void rot_solve_tree_kernel(uint32_t n_views, 
     double rz = 0.0;
 #pragma unroll
     for (int j = 0; j < kTreeOwn; ++j) { p[j] = z[j]; rz += r[j] * z[j]; }
-    rz = block_sum_1024(rz, red, tid);
+    rz = block_wave_sum_1024(rz, red, tid);
     const double rz0 = rz;
     uint32_t it = 0;
     for (; it < cg_iters; ++it) {
@@ -446,7 +396,7 @@ __global__ __launch_bounds__(1024) void rot_solve_tree_kernel(uint32_t n_views, 
             q[j] = y;
             pAp += p[j] * y;
         }
-        pAp = block_sum_1024(pAp, red, tid);
+        pAp = block_wave_sum_1024(pAp, red, tid);
         const double alpha = pAp > 0.0 ? rz / pAp : 0.0;
 #pragma unroll
         for (int j = 0; j < kTreeOwn; ++j) {
@@ -457,7 +407,7 @@ __global__ __launch_bounds__(1024) void rot_solve_tree_kernel(uint32_t n_views, 
         double rzn = 0.0;
 #pragma unroll
         for (int j = 0; j < kTreeOwn; ++j) rzn += r[j] * z[j];
-        rzn = block_sum_1024(rzn, red, tid);
+        rzn = block_wave_sum_1024(rzn, red, tid);
         const double beta = rz > 0.0 ? rzn / rz : 0.0;
 #pragma unroll
         for (int j = 0; j < kTreeOwn; ++j) p[j] = z[j] + beta * p[j];
@@ -481,38 +431,39 @@ struct CgState {
 };
 constexpr int kCgBlock = 256;
 
-__device__ void block_sum3_256(double v[3], double* red /* 3*256 */, int tid) {
-    red[tid] = v[0];
-    red[256 + tid] = v[1];
-    red[512 + tid] = v[2];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[tid] += red[tid + s];
-            red[256 + tid] += red[256 + tid + s];
-            red[512 + tid] += red[512 + tid + s];
-        }
-        __syncthreads();
-    }
-    v[0] = red[0];
-    v[1] = red[256];
-    v[2] = red[512];
-    __syncthreads();
-}
-
 constexpr int kRowLanes = 16;
 constexpr int kRowsPerBlock = kCgBlock / kRowLanes;
+constexpr uint32_t kMaxAggregates = 128;  // of the two-level preconditioner (below); ids stay below kNoAggregate
+
+// What the two-level kernels take on top of the one-level ones (see "two-level PCG" below).  cs_*: rho | kappa | c, 3 n_agg
+// each, by launch parity.
+struct CoarseLevel {
+    uint32_t n_agg;
+    const uint8_t* adj_agg;       // per incidence: the aggregate of its other end (kNoAggregate: a gauge view)
+    const uint32_t* agg_block;    // n_agg + 1 block starts
+    const uint8_t* agg_of_block;
+    const double* Ainv;
+    const double* rpart;          // block sums of r0 (the init kernel's)
+    const double* cs_prev;
+    double* cs_next;
+};
+struct NoCoarseLevel {};
+template <bool TWO_LEVEL>
+using CoarseArgs = std::conditional_t<TWO_LEVEL, CoarseLevel, NoCoarseLevel>;
 
 // assemble diag / rhs (kRowLanes lanes share a view's incidences: one thread walking the tens of incidences of a dense scene
-// graph's view took 47 us per outer step), x = 0, r = b, p = z = r / diag, q0 = s0 = 0, the PCG state records cleared
+// graph's view took 47 us per outer step), x = 0, r = b, q0 = s0 = 0, the PCG state records cleared.  One level: p = z = r /
+// diag.  Two levels (rows in place of views): p = 0 and the block sums of r (-> rho0 = P^T r0) in rpart.
+template <bool TWO_LEVEL>
 __global__ __launch_bounds__(kCgBlock) void cg_init_kernel(uint32_t n_views, const uint32_t* __restrict__ adj_ptr,
                                                            const uint32_t* __restrict__ adj_edge,
                                                            const int8_t* __restrict__ adj_sign,
                                                            const uint8_t* __restrict__ is_root,
                                                            const double* __restrict__ omega, const double* __restrict__ w,
                                                            double* __restrict__ diag, double* __restrict__ x,
-                                                           double* __restrict__ r, double* __restrict__ p, double* __restrict__ q0,
-                                                           double* __restrict__ s0, CgState* __restrict__ states) {
+                                                           double* __restrict__ r, double* __restrict__ p, double* __restrict__ rpart,
+                                                           double* __restrict__ q0, double* __restrict__ s0,
+                                                           CgState* __restrict__ states) {
     const int tid = threadIdx.x, sub = tid & (kRowLanes - 1);
     const uint32_t k = blockIdx.x * kRowsPerBlock + (uint32_t)(tid / kRowLanes);
     if (blockIdx.x == 0 && tid < 3) states[tid] = CgState{};  // the two launch parities and the record the host reads
@@ -525,12 +476,9 @@ __global__ __launch_bounds__(kCgBlock) void cg_init_kernel(uint32_t n_views, con
 #pragma unroll
             for (int c = 0; c < 3; ++c) b[c] += sg * we * omega[3 * (size_t)e + c];
         }
-#pragma unroll
-    for (int m = 1; m < kRowLanes; m <<= 1) {
-        d += __shfl_xor(d, m);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) b[c] += __shfl_xor(b[c], m);
-    }
+    row_lanes_sum<1, kRowLanes>(&d);
+    row_lanes_sum<3, kRowLanes>(b);
+    double rs[3] = {0, 0, 0};
     if (k < n_views && sub == 0) {
         diag[k] = d;
         const double inv = d > 0.0 ? 1.0 / d : 0.0;
@@ -539,9 +487,16 @@ __global__ __launch_bounds__(kCgBlock) void cg_init_kernel(uint32_t n_views, con
             const size_t i = 3 * (size_t)k + c;
             x[i] = 0.0;
             r[i] = b[c];
-            p[i] = b[c] * inv;
+            p[i] = TWO_LEVEL ? 0.0 : b[c] * inv;
             q0[i] = s0[i] = 0.0;
+            rs[c] = b[c];
         }
+    }
+    if constexpr (TWO_LEVEL) {
+        __shared__ double red[3 * kCgBlock];
+        block_tree_sum<3, kCgBlock>(rs, red, tid);
+        if (tid == 0)
+            for (int c = 0; c < 3; ++c) rpart[3 * (size_t)blockIdx.x + c] = rs[c];
     }
 }
 
@@ -557,53 +512,73 @@ __global__ __launch_bounds__(kCgBlock) void cg_init_kernel(uint32_t n_views, con
 //     so the vector update needs no launch of its own (r, q, s are double-buffered: neighbours read the old ones);
 //   * kRowLanes lanes share a view -- a view of a dense scene graph has tens of neighbours, and one thread walking
 //     them is a chain of dependent gathers (40 us per product at V = 5000); the partial rows are combined by a fixed
-//     xor tree;
-//   * the fixed-order sum of the block partials is done by whichever workgroup delivers last (ticket counter).
+//     xor tree (row_lanes_sum);
+//   * a launch only WRITES its block's partials (gamma, delta per axis; with two levels also the block's sum of s); the
+//     NEXT launch starts by reducing the previous launch's partials -- every workgroup redundantly, in the same fixed
+//     order (strided sums, then the 256-entry tree), so every workgroup holds the same bits -- and derives alpha, beta and
+//     the stopping test from them.  (A grid-wide hand-over at the end of the launch instead -- fence, ticket, the last
+//     workgroup reduces -- put an atomic and a serial tail on the critical path of a 15 us kernel.)  Partials and the scalar
+//     state are double-buffered by launch parity, so nothing is read and written in the same launch.
 // Everything is a fixed function of the graph: same input, same bits, on any number of ranks.
-// Sum of 256 values per component (6 components) with EXACTLY the association of block_sum3_256's tree -- entry t takes
-// entry t + s for s = 128, 64, ..., 1 -- but with two barriers instead of eighteen: the two upper steps go through LDS, the
-// six lower ones are shuffles inside wavefront 0 (lane t + lane t + s for t < s is the same addition).  Every thread
-// returns the block's sums.
-__device__ void block_sum6_256(double v[6], double* red /* 6 * 256 */, int tid) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) red[256 * c + tid] = v[c];
-    __syncthreads();
-    if (tid < 128) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) red[256 * c + tid] += red[256 * c + tid + 128];
+struct CgScalars {
+    double alpha[3], beta[3];
+    bool stop;  // converged, now or earlier: the launch has nothing more to do
+};
+// The head of every launch but the init pass: the scalars of this iteration from the block partials (STRIDE doubles per block,
+// gamma and delta leading) of the PREVIOUS launch, and the state record written by workgroup 0.  red: 6 * kCgBlock doubles.
+template <int STRIDE>
+RDEV CgScalars cg_scalars_from_partials(const double* __restrict__ part_prev, uint32_t n_blocks, int prev_was_init, double tol,
+                                        const CgState* __restrict__ st_prev, CgState* __restrict__ st_next, double* red, int tid) {
+    CgScalars sc{{0, 0, 0}, {0, 0, 0}, true};
+    if (st_prev->done) {  // (uniform) converged earlier: keep the record where the host reads it
+        if (blockIdx.x == 0 && tid == 0) *st_next = *st_prev;
+        return sc;
     }
-    __syncthreads();
-    if (tid < 64) {
+    double v[6];
+    strided_sum<6, kCgBlock>(part_prev, n_blocks, STRIDE, tid, v);
+    block_tree_sum<6, kCgBlock>(v, red, tid, TreeInWave0{});
+    bool done = true;
+    double rz_new[3], rz0[3];
 #pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            double x = red[256 * c + tid] + red[256 * c + tid + 64];
-#pragma unroll
-            for (int sft = 32; sft >= 1; sft >>= 1) x += __shfl_down(x, sft);  // lane t (< sft) gets x_t + x_{t + sft}
-            if (tid == 0) red[256 * c] = x;
+    for (int c = 0; c < 3; ++c) {
+        const double g = v[c], dl = v[3 + c];
+        if (prev_was_init) {
+            rz0[c] = g;
+            sc.beta[c] = 0.0;
+            sc.alpha[c] = dl > 0.0 ? g / dl : 0.0;
+            done &= !(g > 0.0);
+        } else {
+            rz0[c] = st_prev->rz0[c];
+            const double a_prev = st_prev->alpha[c];
+            const double bt = st_prev->rz[c] > 0.0 ? g / st_prev->rz[c] : 0.0;
+            const double den = a_prev != 0.0 ? dl - bt * g / a_prev : dl;
+            sc.beta[c] = bt;
+            sc.alpha[c] = den > 0.0 ? g / den : 0.0;
+            done &= !(g > tol * tol * rz0[c]);
         }
+        rz_new[c] = g;
     }
-    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) {
 #pragma unroll
-    for (int c = 0; c < 6; ++c) v[c] = red[256 * c];
-    __syncthreads();
+        for (int c = 0; c < 3; ++c) {
+            st_next->rz[c] = rz_new[c];
+            st_next->rz0[c] = rz0[c];
+            st_next->alpha[c] = sc.alpha[c];
+            st_next->beta[c] = sc.beta[c];
+        }
+        st_next->iters = prev_was_init ? 0.0 : st_prev->iters + 1.0;
+        st_next->done = done;
+        st_next->mean_step = 0.0;
+        st_next->ticket = 0;
+    }
+    sc.stop = done;
+    return sc;
 }
 
-// The scalars of one PCG iteration, derived from the block partials (gamma, delta per axis) of the PREVIOUS launch.
-struct CgScalars {
-    double alpha[3], beta[3], rz[3], rz0[3], iters;
-    bool done;
-};
-
-// ONE launch per PCG iteration (round 4 form).  Round 3 ended every launch with a grid-wide hand-over: each workgroup
-// published its partial sums behind an agent-scope fence, took a ticket, and the last one to arrive reduced all partials and
-// wrote the next scalars -- a fence, an atomic and a serial tail on the critical path of a 15 us kernel.  Now a launch only
-// WRITES its block's partials; the NEXT launch starts by reducing the previous launch's partials -- every workgroup
-// redundantly, in the same fixed order (strided sums, then the 256-entry tree), so every workgroup holds the same bits --
-// and derives alpha, beta and the stopping test from them.  Partials and the scalar state are double-buffered by launch
-// parity, so nothing is read and written in the same launch.  mode 1: the init pass (alpha = beta = 0; x and r stay, p
-// becomes z, q becomes 0: produces s0 = A z0 and the partials of gamma0, delta0); mode 0: an iteration; mode 2: only the
-// reduction and the state record (what the host reads between chunks of launches), no vector is touched.
-// Same arithmetic in the same order as the round-3 kernel: the rotations are bit-identical.
+// mode 1: the init pass (alpha = beta = 0; x and r stay, p becomes z, q becomes 0: produces s0 = A z0 and the partials of
+// gamma0, delta0); mode 0: an iteration; mode 2: only the reduction and the state record (what the host reads between chunks
+// of launches), no vector is touched.  TWO_LEVEL: rows in place of views, and the coarse correction of "two-level PCG" below.
+template <bool TWO_LEVEL>
 __global__ __launch_bounds__(kCgBlock) void cg_iteration_kernel(uint32_t n_views, const uint32_t* __restrict__ adj_ptr,
                                                                 const uint32_t* __restrict__ adj_edge,
                                                                 const uint32_t* __restrict__ adj_other,
@@ -614,87 +589,130 @@ __global__ __launch_bounds__(kCgBlock) void cg_iteration_kernel(uint32_t n_views
                                                                 double* s_new, int mode, int prev_was_init, double tol,
                                                                 const double* __restrict__ part_prev, double* __restrict__ part_next,
                                                                 uint32_t n_blocks, const CgState* __restrict__ st_prev,
-                                                                CgState* __restrict__ st_next) {
-    __shared__ double red[6 * kCgBlock];
+                                                                CgState* __restrict__ st_next, CoarseArgs<TWO_LEVEL> coarse) {
+    constexpr int NP = TWO_LEVEL ? 9 : 6;  // partials per block: gamma (3), delta (3), two levels: the block's sum of s (3)
+    __shared__ double lds[NP * kCgBlock + (TWO_LEVEL ? 12 * kMaxAggregates : 0)];
+    double* const red = lds;
     const int tid = threadIdx.x, sub = tid & (kRowLanes - 1);
-    double alpha[3] = {0, 0, 0}, beta[3] = {0, 0, 0};
+    CgScalars sc{{0, 0, 0}, {0, 0, 0}, false};
     if (mode != 1) {
-        if (st_prev->done) {  // (uniform) converged earlier: keep the record where the host reads it
-            if (blockIdx.x == 0 && tid == 0) *st_next = *st_prev;
-            return;
-        }
-        double v[6] = {0, 0, 0, 0, 0, 0};
-        for (uint32_t b = tid; b < n_blocks; b += kCgBlock)
+        sc = cg_scalars_from_partials<NP>(part_prev, n_blocks, prev_was_init, tol, st_prev, st_next, red, tid);
+        if (sc.stop || mode == 2) return;  // (uniform)
+    }
+    const double* const alpha = sc.alpha;
+    const double* const beta = sc.beta;
+    double c_old[3] = {0, 0, 0}, c_own[3] = {0, 0, 0};  // two levels: c of this block's aggregate, last launch's and this one's
+    [[maybe_unused]] double* const l_c = lds + (TWO_LEVEL ? NP * kCgBlock + 3 * kMaxAggregates : 0);  // c = Ac^-1 rho
+    if constexpr (TWO_LEVEL) {
+        const uint32_t n_agg = coarse.n_agg;
+        const uint32_t* __restrict__ agg_block = coarse.agg_block;
+        const double* __restrict__ Ainv = coarse.Ainv;
+        const double* __restrict__ cs_prev = coarse.cs_prev;
+        double* __restrict__ cs_next = coarse.cs_next;
+        double* const l_rho = lds + NP * kCgBlock;
+        double(*const l_half)[3 * kMaxAggregates] = reinterpret_cast<double(*)[3 * kMaxAggregates]>(l_c + 3 * kMaxAggregates);
+        // the coarse vectors of this iteration
+        if (tid < (int)n_agg) {
+            double rho[3] = {0, 0, 0}, kap[3] = {0, 0, 0};
+            if (mode == 1) {
+                const double* __restrict__ rpart = coarse.rpart;
+                for (uint32_t b = agg_block[tid]; b < agg_block[tid + 1]; ++b)
 #pragma unroll
-            for (int c = 0; c < 6; ++c) v[c] += part_prev[6 * (size_t)b + c];
-        block_sum6_256(v, red, tid);
-        bool done = true;
-        double rz_new[3], rz0[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double g = v[c], dl = v[3 + c];
-            if (prev_was_init) {
-                rz0[c] = g;
-                beta[c] = 0.0;
-                alpha[c] = dl > 0.0 ? g / dl : 0.0;
-                done &= !(g > 0.0);
+                    for (int c = 0; c < 3; ++c) rho[c] += rpart[3 * (size_t)b + c];
             } else {
-                rz0[c] = st_prev->rz0[c];
-                const double a_prev = st_prev->alpha[c];
-                const double bt = st_prev->rz[c] > 0.0 ? g / st_prev->rz[c] : 0.0;
-                const double den = a_prev != 0.0 ? dl - bt * g / a_prev : dl;
-                beta[c] = bt;
-                alpha[c] = den > 0.0 ? g / den : 0.0;
-                done &= !(g > tol * tol * rz0[c]);
+                double sig[3] = {0, 0, 0};
+                for (uint32_t b = agg_block[tid]; b < agg_block[tid + 1]; ++b)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sig[c] += part_prev[9 * (size_t)b + 6 + c];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    kap[c] = sig[c] + beta[c] * cs_prev[3 * (size_t)n_agg + 3 * tid + c];
+                    rho[c] = cs_prev[3 * tid + c] - alpha[c] * kap[c];
+                }
             }
-            rz_new[c] = g;
-        }
-        if (blockIdx.x == 0 && tid == 0) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                st_next->rz[c] = rz_new[c];
-                st_next->rz0[c] = rz0[c];
-                st_next->alpha[c] = alpha[c];
-                st_next->beta[c] = beta[c];
+                l_rho[3 * tid + c] = rho[c];
+                if (blockIdx.x == 0) {
+                    cs_next[3 * tid + c] = rho[c];
+                    cs_next[3 * (size_t)n_agg + 3 * tid + c] = kap[c];
+                }
             }
-            st_next->iters = prev_was_init ? 0.0 : st_prev->iters + 1.0;
-            st_next->done = done;
-            st_next->mean_step = 0.0;
-            st_next->ticket = 0;
         }
-        if (done || mode == 2) return;  // (uniform)
+        __syncthreads();
+        {   // c = Ac^-1 rho: thread (a, half) sums half of the columns (Ac^-1 read through its symmetric counterpart, so that
+            // consecutive lanes read consecutive words)
+            const uint32_t a = (uint32_t)tid & (kMaxAggregates - 1), h = (uint32_t)tid >> 7, half = (n_agg + 1) / 2;
+            const uint32_t b0 = h * half, b1 = min(n_agg, b0 + half);
+            double acc[3] = {0, 0, 0};
+            if (a < n_agg) {
+                for (uint32_t b = b0; b < b1; ++b) {
+                    const double m = Ainv[(size_t)b * n_agg + a];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[c] += m * l_rho[3 * b + c];
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) l_half[h][3 * a + c] = acc[c];
+            }
+        }
+        __syncthreads();
+        if (tid < (int)n_agg) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double cn = l_half[0][3 * tid + c] + l_half[1][3 * tid + c];
+                l_c[3 * tid + c] = cn;
+                if (blockIdx.x == 0) cs_next[6 * (size_t)n_agg + 3 * tid + c] = cn;
+            }
+        }
+        __syncthreads();
+        const uint32_t my_agg = coarse.agg_of_block[blockIdx.x];
+        if (my_agg != kNoAggregate) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                c_own[c] = l_c[3 * my_agg + c];
+                c_old[c] = mode == 1 ? c_own[c] : cs_prev[6 * (size_t)n_agg + 3 * my_agg + c];
+            }
+        }
     }
     const uint32_t k = blockIdx.x * kRowsPerBlock + (uint32_t)(tid / kRowLanes);
-    double gd[6] = {0, 0, 0, 0, 0, 0};  // gamma (3), delta (3)
+    double gd[NP] = {};
     if (k < n_views) {
         const bool free_k = !is_root[k];
         // neighbours: their new z, rebuilt from the old vectors
         double y[3] = {0, 0, 0};
         if (free_k)
             for (uint32_t a = adj_ptr[k] + (uint32_t)sub; a < adj_ptr[k + 1]; a += kRowLanes) {
+                uint32_t ag = 0;
+                if constexpr (TWO_LEVEL) {
+                    ag = coarse.adj_agg[a];
+                    if (ag == kNoAggregate) continue;  // a gauge view
+                }
                 const uint32_t o = adj_other[a];
-                if (is_root[o]) continue;
+                if constexpr (!TWO_LEVEL)
+                    if (is_root[o]) continue;
                 const double we = w[adj_edge[a]], dn = diag[o], inv = dn > 0.0 ? 1.0 / dn : 0.0;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const size_t i = 3 * (size_t)o + c;
                     const double qo = s_old[i] + beta[c] * q_old[i];
-                    y[c] -= we * ((r_old[i] - alpha[c] * qo) * inv);
+                    if constexpr (TWO_LEVEL) y[c] -= we * ((r_old[i] - alpha[c] * qo) * inv + l_c[3 * ag + c]);
+                    else y[c] -= we * ((r_old[i] - alpha[c] * qo) * inv);
                 }
             }
-#pragma unroll
-        for (int m = 1; m < kRowLanes; m <<= 1)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) y[c] += __shfl_xor(y[c], m);
+        row_lanes_sum<3, kRowLanes>(y);
         if (sub == 0) {  // the view's own entries of every vector
             const double d = diag[k], inv = d > 0.0 ? 1.0 / d : 0.0;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const size_t i = 3 * (size_t)k + c;
                 const double ro = r_old[i];
-                const double pk = ro * inv + beta[c] * p[i];
+                double zo = ro * inv;
+                if constexpr (TWO_LEVEL) zo = free_k ? ro * inv + c_old[c] : 0.0;
+                const double pk = zo + beta[c] * p[i];
                 const double qk = s_old[i] + beta[c] * q_old[i];
-                const double rn = ro - alpha[c] * qk, zn = rn * inv;
+                const double rn = ro - alpha[c] * qk;
+                double zn = rn * inv;
+                if constexpr (TWO_LEVEL) zn = free_k ? rn * inv + c_own[c] : 0.0;
                 const double sn = free_k ? d * zn + y[c] : 0.0;
                 p[i] = pk;
                 q_new[i] = qk;
@@ -703,13 +721,14 @@ __global__ __launch_bounds__(kCgBlock) void cg_iteration_kernel(uint32_t n_views
                 s_new[i] = sn;
                 gd[c] = rn * zn;
                 gd[3 + c] = zn * sn;
+                if constexpr (TWO_LEVEL) gd[6 + c] = sn;
             }
         }
     }
-    block_sum6_256(gd, red, tid);
+    block_tree_sum<NP, kCgBlock>(gd, red, tid, TreeInWave0{});
     if (tid == 0)
 #pragma unroll
-        for (int c = 0; c < 6; ++c) part_next[6 * (size_t)blockIdx.x + c] = gd[c];
+        for (int c = 0; c < NP; ++c) part_next[NP * (size_t)blockIdx.x + c] = gd[c];
 }
 
 // (gate: a record of the PCG state on the device, or null.  With a gate the kernel runs only if that solve has converged: the
@@ -726,24 +745,28 @@ __global__ __launch_bounds__(kCgBlock) void cg_step_norm_kernel(uint32_t n_views
     if (k < n_views)
         nd[0] = sqrt(x[3 * (size_t)k] * x[3 * (size_t)k] + x[3 * (size_t)k + 1] * x[3 * (size_t)k + 1] +
                      x[3 * (size_t)k + 2] * x[3 * (size_t)k + 2]);
-    block_sum3_256(nd, red, tid);
+    block_tree_sum<3, kCgBlock>(nd, red, tid);
     if (tid == 0)
         for (int c = 0; c < 3; ++c) partial[3 * blockIdx.x + c] = nd[c];
 }
 
-__global__ __launch_bounds__(256) void rot_update_kernel(uint32_t n_views, const double* __restrict__ x,
-                                                         double* __restrict__ R, const CgState* __restrict__ gate,
-                                                         const int* __restrict__ veto) {
+// R_view <- R_view exp(x_k).  row_view: null = x is in view numbering; else the view of row k of the two-level solve's
+// renumbering (0xFFFFFFFF: a padding row, no view).
+__global__ __launch_bounds__(256) void rot_update_kernel(uint32_t n_rows, const double* __restrict__ x,
+                                                         const uint32_t* __restrict__ row_view, double* __restrict__ R,
+                                                         const CgState* __restrict__ gate, const int* __restrict__ veto) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= n_views || (gate && !gate->done) || (veto && *veto)) return;
+    if (k >= n_rows || (gate && !gate->done) || (veto && *veto)) return;
+    const uint32_t v = row_view ? row_view[k] : k;
+    if (v == 0xFFFFFFFFu) return;
     double Rk[9], Ex[9], Rn[9];
     const double wv[3] = {x[3 * (size_t)k], x[3 * (size_t)k + 1], x[3 * (size_t)k + 2]};
 #pragma unroll
-    for (int c = 0; c < 9; ++c) Rk[c] = R[9 * (size_t)k + c];
+    for (int c = 0; c < 9; ++c) Rk[c] = R[9 * (size_t)v + c];
     so3_exp(wv, Ex);
     mat3_mul(Rk, Ex, Rn);
 #pragma unroll
-    for (int c = 0; c < 9; ++c) R[9 * (size_t)k + c] = Rn[c];
+    for (int c = 0; c < 9; ++c) R[9 * (size_t)v + c] = Rn[c];
 }
 
 // ---- two-level PCG (dense, band-like view graphs: every Jacobi solve runs into the cap) ----------------------------------
@@ -760,77 +783,8 @@ __global__ __launch_bounds__(256) void rot_update_kernel(uint32_t n_views, const
 //   * every workgroup applies Ac^-1 to rho' (<= 128 x 128 doubles from L2, read through the symmetric counterpart so that
 //     consecutive lanes read consecutive words) and keeps c = Ac^-1 rho' in LDS; a neighbour's rebuilt z gets c of ITS aggregate
 //     (the aggregate id travels with the incidence), the view's own z the block's.
-// Same input, same bits: no atomics, every sum in a fixed order.
-constexpr uint32_t kMaxAggregates = 128;
-constexpr uint8_t kNoAggregate = 255;
-
-__device__ void block_sum9_256(double v[9], double* red /* 9 * 256 */, int tid) {  // the tree of block_sum6_256, nine components
-#pragma unroll
-    for (int c = 0; c < 9; ++c) red[256 * c + tid] = v[c];
-    __syncthreads();
-    if (tid < 128) {
-#pragma unroll
-        for (int c = 0; c < 9; ++c) red[256 * c + tid] += red[256 * c + tid + 128];
-    }
-    __syncthreads();
-    if (tid < 64) {
-#pragma unroll
-        for (int c = 0; c < 9; ++c) {
-            double x = red[256 * c + tid] + red[256 * c + tid + 64];
-#pragma unroll
-            for (int sft = 32; sft >= 1; sft >>= 1) x += __shfl_down(x, sft);
-            if (tid == 0) red[256 * c] = x;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 9; ++c) v[c] = red[256 * c];
-    __syncthreads();
-}
-
-// diag / rhs per row (kRowLanes lanes share a row), x = 0, r = b, p = 0; block sums of r (-> rho0 = P^T r0)
-__global__ __launch_bounds__(kCgBlock) void cg2_init_kernel(uint32_t n_rows, const uint32_t* __restrict__ adj_ptr,
-                                                            const uint32_t* __restrict__ adj_edge, const int8_t* __restrict__ adj_sign,
-                                                            const uint8_t* __restrict__ is_root, const double* __restrict__ omega,
-                                                            const double* __restrict__ w, double* __restrict__ diag,
-                                                            double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
-                                                            double* __restrict__ rpart, double* __restrict__ q0, double* __restrict__ s0,
-                                                            CgState* __restrict__ states) {
-    __shared__ double red[3 * kCgBlock];
-    const int tid = threadIdx.x, sub = tid & (kRowLanes - 1);
-    const uint32_t k = blockIdx.x * kRowsPerBlock + (uint32_t)(tid / kRowLanes);
-    if (blockIdx.x == 0 && tid < 3) states[tid] = CgState{};
-    double d = 0, b[3] = {0, 0, 0};
-    if (k < n_rows && !is_root[k])
-        for (uint32_t a = adj_ptr[k] + (uint32_t)sub; a < adj_ptr[k + 1]; a += kRowLanes) {
-            const uint32_t e = adj_edge[a];
-            const double we = w[e], sg = (double)adj_sign[a];
-            d += we;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) b[c] += sg * we * omega[3 * (size_t)e + c];
-        }
-#pragma unroll
-    for (int m = 1; m < kRowLanes; m <<= 1) {
-        d += __shfl_xor(d, m);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) b[c] += __shfl_xor(b[c], m);
-    }
-    double rs[3] = {0, 0, 0};
-    if (k < n_rows && sub == 0) {
-        diag[k] = d;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            x[3 * (size_t)k + c] = 0.0;
-            r[3 * (size_t)k + c] = b[c];
-            p[3 * (size_t)k + c] = 0.0;
-            q0[3 * (size_t)k + c] = s0[3 * (size_t)k + c] = 0.0;
-            rs[c] = b[c];
-        }
-    }
-    block_sum3_256(rs, red, tid);
-    if (tid == 0)
-        for (int c = 0; c < 3; ++c) rpart[3 * (size_t)blockIdx.x + c] = rs[c];
-}
+// Same input, same bits: no atomics, every sum in a fixed order.  The kernels: cg_init_kernel<true> and
+// cg_iteration_kernel<true> above; the coarse matrix's assembly and inversion here.
 
 // Ac = P^T A P: workgroup a owns row a.  The incidences of the aggregate's rows are one contiguous range of the adjacency: the
 // threads stage (column, weight) of a chunk of it in LDS side by side, then thread (b, segment) adds what falls into column b
@@ -978,196 +932,6 @@ __global__ __launch_bounds__(1024) void cg2_coarse_invert_kernel(uint32_t n, con
     if (tid == 0) *status = bad ? 1 : 0;
 }
 
-// One launch per iteration, as cg_iteration_kernel (modes 1 / 0 / 2, scalars from the previous launch's partials), with the
-// coarse correction.  Partials per block: gamma (3), delta (3), the block's sum of s (3).  cs_*: rho | kappa | c, 3 n_agg each.
-__global__ __launch_bounds__(kCgBlock) void cg2_iteration_kernel(
-    uint32_t n_rows, const uint32_t* __restrict__ adj_ptr, const uint32_t* __restrict__ adj_edge, const uint32_t* __restrict__ adj_other,
-    const uint8_t* __restrict__ adj_agg, const uint8_t* __restrict__ is_root, const double* __restrict__ w, const double* __restrict__ diag,
-    double* __restrict__ x, double* __restrict__ p, const double* r_old, double* r_new, const double* q_old, double* q_new,
-    const double* s_old, double* s_new, int mode, int prev_was_init, double tol, const double* __restrict__ part_prev,
-    double* __restrict__ part_next, uint32_t n_blocks, const CgState* __restrict__ st_prev, CgState* __restrict__ st_next, uint32_t n_agg,
-    const uint32_t* __restrict__ agg_block, const uint8_t* __restrict__ agg_of_block, const double* __restrict__ Ainv,
-    const double* __restrict__ rpart, const double* __restrict__ cs_prev, double* __restrict__ cs_next) {
-    __shared__ double red[9 * kCgBlock];
-    __shared__ double l_rho[3 * kMaxAggregates], l_c[3 * kMaxAggregates], l_half[2][3 * kMaxAggregates];
-    const int tid = threadIdx.x, sub = tid & (kRowLanes - 1);
-    double alpha[3] = {0, 0, 0}, beta[3] = {0, 0, 0};
-    if (mode != 1) {
-        if (st_prev->done) {  // (uniform) converged earlier: keep the record where the host reads it
-            if (blockIdx.x == 0 && tid == 0) *st_next = *st_prev;
-            return;
-        }
-        double v[6] = {0, 0, 0, 0, 0, 0};
-        for (uint32_t b = tid; b < n_blocks; b += kCgBlock)
-#pragma unroll
-            for (int c = 0; c < 6; ++c) v[c] += part_prev[9 * (size_t)b + c];
-        block_sum6_256(v, red, tid);
-        bool done = true;
-        double rz_new[3], rz0[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double g = v[c], dl = v[3 + c];
-            if (prev_was_init) {
-                rz0[c] = g;
-                beta[c] = 0.0;
-                alpha[c] = dl > 0.0 ? g / dl : 0.0;
-                done &= !(g > 0.0);
-            } else {
-                rz0[c] = st_prev->rz0[c];
-                const double a_prev = st_prev->alpha[c];
-                const double bt = st_prev->rz[c] > 0.0 ? g / st_prev->rz[c] : 0.0;
-                const double den = a_prev != 0.0 ? dl - bt * g / a_prev : dl;
-                beta[c] = bt;
-                alpha[c] = den > 0.0 ? g / den : 0.0;
-                done &= !(g > tol * tol * rz0[c]);
-            }
-            rz_new[c] = g;
-        }
-        if (blockIdx.x == 0 && tid == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                st_next->rz[c] = rz_new[c];
-                st_next->rz0[c] = rz0[c];
-                st_next->alpha[c] = alpha[c];
-                st_next->beta[c] = beta[c];
-            }
-            st_next->iters = prev_was_init ? 0.0 : st_prev->iters + 1.0;
-            st_next->done = done;
-            st_next->mean_step = 0.0;
-            st_next->ticket = 0;
-        }
-        if (done || mode == 2) return;  // (uniform)
-    }
-    // the coarse vectors of this iteration
-    if (tid < (int)n_agg) {
-        double rho[3] = {0, 0, 0}, kap[3] = {0, 0, 0};
-        if (mode == 1) {
-            for (uint32_t b = agg_block[tid]; b < agg_block[tid + 1]; ++b)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) rho[c] += rpart[3 * (size_t)b + c];
-        } else {
-            double sig[3] = {0, 0, 0};
-            for (uint32_t b = agg_block[tid]; b < agg_block[tid + 1]; ++b)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) sig[c] += part_prev[9 * (size_t)b + 6 + c];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                kap[c] = sig[c] + beta[c] * cs_prev[3 * (size_t)n_agg + 3 * tid + c];
-                rho[c] = cs_prev[3 * tid + c] - alpha[c] * kap[c];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            l_rho[3 * tid + c] = rho[c];
-            if (blockIdx.x == 0) {
-                cs_next[3 * tid + c] = rho[c];
-                cs_next[3 * (size_t)n_agg + 3 * tid + c] = kap[c];
-            }
-        }
-    }
-    __syncthreads();
-    {   // c = Ac^-1 rho: thread (a, half) sums half of the columns
-        const uint32_t a = (uint32_t)tid & (kMaxAggregates - 1), h = (uint32_t)tid >> 7, half = (n_agg + 1) / 2;
-        const uint32_t b0 = h * half, b1 = min(n_agg, b0 + half);
-        double acc[3] = {0, 0, 0};
-        if (a < n_agg) {
-            for (uint32_t b = b0; b < b1; ++b) {
-                const double m = Ainv[(size_t)b * n_agg + a];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) acc[c] += m * l_rho[3 * b + c];
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) l_half[h][3 * a + c] = acc[c];
-        }
-    }
-    __syncthreads();
-    if (tid < (int)n_agg) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double cn = l_half[0][3 * tid + c] + l_half[1][3 * tid + c];
-            l_c[3 * tid + c] = cn;
-            if (blockIdx.x == 0) cs_next[6 * (size_t)n_agg + 3 * tid + c] = cn;
-        }
-    }
-    __syncthreads();
-    const uint32_t my_agg = agg_of_block[blockIdx.x];
-    double c_old[3] = {0, 0, 0}, c_own[3] = {0, 0, 0};
-    if (my_agg != kNoAggregate) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            c_own[c] = l_c[3 * my_agg + c];
-            c_old[c] = mode == 1 ? c_own[c] : cs_prev[6 * (size_t)n_agg + 3 * my_agg + c];
-        }
-    }
-    const uint32_t k = blockIdx.x * kRowsPerBlock + (uint32_t)(tid / kRowLanes);
-    double gd[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // gamma (3), delta (3), the sum of s (3)
-    if (k < n_rows) {
-        const bool free_k = !is_root[k];
-        double y[3] = {0, 0, 0};
-        if (free_k)
-            for (uint32_t a = adj_ptr[k] + (uint32_t)sub; a < adj_ptr[k + 1]; a += kRowLanes) {
-                const uint32_t ag = adj_agg[a];
-                if (ag == kNoAggregate) continue;  // a gauge view
-                const uint32_t o = adj_other[a];
-                const double we = w[adj_edge[a]], dn = diag[o], inv = dn > 0.0 ? 1.0 / dn : 0.0;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const size_t i = 3 * (size_t)o + c;
-                    const double qo = s_old[i] + beta[c] * q_old[i];
-                    y[c] -= we * ((r_old[i] - alpha[c] * qo) * inv + l_c[3 * ag + c]);
-                }
-            }
-#pragma unroll
-        for (int m = 1; m < kRowLanes; m <<= 1)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) y[c] += __shfl_xor(y[c], m);
-        if (sub == 0) {
-            const double d = diag[k], inv = d > 0.0 ? 1.0 / d : 0.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const size_t i = 3 * (size_t)k + c;
-                const double ro = r_old[i];
-                const double zo = free_k ? ro * inv + c_old[c] : 0.0;
-                const double pk = zo + beta[c] * p[i];
-                const double qk = s_old[i] + beta[c] * q_old[i];
-                const double rn = ro - alpha[c] * qk;
-                const double zn = free_k ? rn * inv + c_own[c] : 0.0;
-                const double sn = free_k ? d * zn + y[c] : 0.0;
-                p[i] = pk;
-                q_new[i] = qk;
-                x[i] += alpha[c] * pk;
-                r_new[i] = rn;
-                s_new[i] = sn;
-                gd[c] = rn * zn;
-                gd[3 + c] = zn * sn;
-                gd[6 + c] = sn;
-            }
-        }
-    }
-    block_sum9_256(gd, red, tid);
-    if (tid == 0)
-#pragma unroll
-        for (int c = 0; c < 9; ++c) part_next[9 * (size_t)blockIdx.x + c] = gd[c];
-}
-
-// R_view <- R_view exp(x_row) for the renumbered rows (padding rows map to no view)
-__global__ __launch_bounds__(256) void rot_update_rows_kernel(uint32_t n_rows, const double* __restrict__ x, const uint32_t* __restrict__ row_view,
-                                                              double* __restrict__ R, const CgState* __restrict__ gate,
-                                                              const int* __restrict__ veto) {
-    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= n_rows || (gate && !gate->done) || (veto && *veto)) return;
-    const uint32_t v = row_view[k];
-    if (v == 0xFFFFFFFFu) return;
-    double Rk[9], Ex[9], Rn[9];
-    const double wv[3] = {x[3 * (size_t)k], x[3 * (size_t)k + 1], x[3 * (size_t)k + 2]};
-#pragma unroll
-    for (int c = 0; c < 9; ++c) Rk[c] = R[9 * (size_t)v + c];
-    so3_exp(wv, Ex);
-    mat3_mul(Rk, Ex, Rn);
-#pragma unroll
-    for (int c = 0; c < 9; ++c) R[9 * (size_t)v + c] = Rn[c];
-}
-
 // pgi_edge records (status OK) -> rotation-graph edges, all on the device: idx[e] = pair of edge e
 __global__ __launch_bounds__(256) void rot_edges_from_table_kernel(const pgi_edge* __restrict__ table, const uint32_t* __restrict__ idx,
                                                                     const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst,
@@ -1194,78 +958,7 @@ __global__ __launch_bounds__(256) void rot_gather_R_kernel(const RotEdgeDev* __r
     for (int c = 0; c < 9; ++c) out[9 * (size_t)k + c] = e->R[c];
 }
 
-// ---- host: maximum-weight spanning forest + BFS initialisation ----------------------------------------
-struct ForestEdge {
-    uint32_t edge, other;  // other | inv << 31
-};
-// Kruskal on (weight desc, edge index asc); returns the forest's edge list and its adjacency
-static void spanning_forest(uint32_t V, const uint32_t* src, const uint32_t* dst, const double* weight, uint32_t nE,
-                            std::vector<uint32_t>& tree, std::vector<std::vector<ForestEdge>>& adj) {
-    // (weight desc, edge index asc): ONE integer key per edge -- the order-preserving bit pattern of the weight, inverted -- and a
-    // stable sort by it
-    std::vector<uint64_t> key[2] = {std::vector<uint64_t>(nE), std::vector<uint64_t>(nE)};
-    std::vector<uint32_t> idx[2] = {std::vector<uint32_t>(nE), std::vector<uint32_t>(nE)};
-    for (uint32_t e = 0; e < nE; ++e) {
-        uint64_t u;
-        const double wv = weight[e] == 0.0 ? 0.0 : weight[e];  // (-0.0 and +0.0 compare equal: one key)
-        memcpy(&u, &wv, 8);
-        u = (u >> 63) ? ~u : (u | 0x8000000000000000ull);  // ascending in the value
-        key[0][e] = ~u;                                      // descending
-        idx[0][e] = e;
-    }
-    {   // stable least-significant-digit radix sort, 11-bit digits; a digit all keys share is skipped (round 4: std::sort of the
-        // pairs took 5.8 ms at 10^5 edges)
-        constexpr int kBits = 11, kPasses = 6;
-        std::vector<uint32_t> hist((size_t)kPasses << kBits, 0);
-        for (uint32_t e = 0; e < nE; ++e)
-            for (int ps = 0; ps < kPasses; ++ps) ++hist[((size_t)ps << kBits) + ((key[0][e] >> (ps * kBits)) & ((1u << kBits) - 1))];
-        int cur = 0;
-        for (int ps = 0; ps < kPasses; ++ps) {
-            uint32_t* h = &hist[(size_t)ps << kBits];
-            bool single = false;
-            for (uint32_t b = 0; b < (1u << kBits); ++b) single |= h[b] == nE;
-            if (single) continue;
-            uint32_t run = 0;
-            for (uint32_t b = 0; b < (1u << kBits); ++b) {
-                const uint32_t c = h[b];
-                h[b] = run;
-                run += c;
-            }
-            const uint64_t* ks = key[cur].data();
-            const uint32_t* is = idx[cur].data();
-            uint64_t* kd = key[cur ^ 1].data();
-            uint32_t* id = idx[cur ^ 1].data();
-            for (uint32_t e = 0; e < nE; ++e) {
-                const uint32_t pos = h[(ks[e] >> (ps * kBits)) & ((1u << kBits) - 1)]++;
-                kd[pos] = ks[e];
-                id[pos] = is[e];
-            }
-            cur ^= 1;
-        }
-        if (cur) idx[0].swap(idx[1]);
-    }
-    const std::vector<uint32_t>& order = idx[0];
-    std::vector<uint32_t> parent(V);
-    std::iota(parent.begin(), parent.end(), 0u);
-    auto find = [&](uint32_t a) {
-        while (parent[a] != a) {
-            parent[a] = parent[parent[a]];
-            a = parent[a];
-        }
-        return a;
-    };
-    adj.assign(V, {});
-    tree.clear();
-    for (uint32_t e : order) {
-        const uint32_t a = find(src[e]), b = find(dst[e]);
-        if (a == b) continue;
-        parent[std::max(a, b)] = std::min(a, b);
-        adj[src[e]].push_back({e, dst[e]});
-        adj[dst[e]].push_back({e, src[e] | 0x80000000u});
-        tree.push_back(e);
-        if (tree.size() + 1 == V) break;  // spanning: the remaining edges all close cycles
-    }
-}
+// ---- host: BFS initialisation over the maximum-weight spanning forest (spanning_forest: pgi_graph_host.hpp) ----------------
 // BFS over the forest; R_of(e) = pointer to the 9 doubles of edge e's relative rotation
 template <class RofE>
 static void forest_bfs_init(uint32_t V, const std::vector<std::vector<ForestEdge>>& adj, RofE R_of, std::vector<double>& R,
@@ -1302,165 +995,38 @@ static void forest_bfs_init(uint32_t V, const std::vector<std::vector<ForestEdge
     }
 }
 
-// ---- host: the aggregates of the two-level preconditioner and the renumbered adjacency ------------------------------------
-struct TwoLevelPlan {
-    uint32_t n_agg = 0, n_rows = 0, n_blocks = 0;
-    std::vector<uint32_t> row_view;                 // row -> view, 0xFFFFFFFF = padding
-    std::vector<uint32_t> ptr, aedge, aother;       // the adjacency of the rows (incidences in the views' order)
-    std::vector<int8_t> asign;
-    std::vector<uint8_t> aagg, root, agg_of_block;  // aggregate of the incidence's other end / of the block; row is inert
-    std::vector<uint32_t> agg_block;                // n_agg + 1 block starts
-};
-// Breadth-first order of all views from the gauge views; returns the depth of the deepest view.  A band-like graph (views along
-// a walk or a ring) is deep -- V / reach levels -- a densely connected one has a handful of levels.
-static uint32_t bfs_from_gauge_views(uint32_t V, const std::vector<uint32_t>& ptr, const std::vector<uint32_t>& aother,
-                                     const std::vector<uint8_t>& is_root, std::vector<uint32_t>& order) {
-    order.clear();
-    order.reserve(V);
-    std::vector<uint32_t> level(V, 0xFFFFFFFFu);
-    for (uint32_t v = 0; v < V; ++v)
-        if (is_root[v]) { level[v] = 0; order.push_back(v); }
-    uint32_t depth = 0;
-    for (size_t h = 0; h < order.size(); ++h) {
-        const uint32_t u = order[h];
-        for (uint32_t a = ptr[u]; a < ptr[u + 1]; ++a) {
-            const uint32_t o = aother[a];
-            if (level[o] != 0xFFFFFFFFu) continue;
-            level[o] = level[u] + 1;
-            depth = std::max(depth, level[o]);
-            order.push_back(o);
-        }
-    }
-    for (uint32_t v = 0; v < V; ++v)
-        if (level[v] == 0xFFFFFFFFu) order.push_back(v);  // (not reachable from a gauge view: cannot happen, kept for safety)
-    return depth;
-}
-// Aggregates by region growing: seeds in breadth-first order from the gauge views (`order`), each aggregate the first `target`
-// free views a breadth-first walk from its seed reaches among the unassigned ones; left-overs below half the target join
-// their smallest neighbouring aggregate.  false when the graph needs more than kMaxAggregates - 1 (many components).
-static bool plan_two_level(uint32_t V, const std::vector<uint32_t>& ptr, const std::vector<uint32_t>& aedge,
-                           const std::vector<uint32_t>& aother, const std::vector<int8_t>& asign, const std::vector<uint8_t>& is_root,
-                           const std::vector<uint32_t>& order, TwoLevelPlan& out) {
-    uint32_t n_free = 0;
-    for (uint32_t v = 0; v < V; ++v) n_free += is_root[v] ? 0u : 1u;
-    if (n_free == 0) return false;
-    const uint32_t kNone = 0xFFFFFFFFu;
-    uint32_t target = std::max<uint32_t>(32u, (n_free + 111u) / 112u);
-    target = (target + kRowsPerBlock - 1) / kRowsPerBlock * kRowsPerBlock;
-    std::vector<uint32_t> agg, disc, size, into, final_id;  // disc: the free views in the order the walks reached them
-    uint32_t n_final = 0;
-    auto label = [&](uint32_t g) {  // the aggregate a merged one ended up in
-        while (into[g] != g) g = into[g] = into[into[g]];
-        return g;
-    };
-    for (int attempt = 0;; ++attempt) {
-        agg.assign(V, kNone);
-        disc.clear();
-        disc.reserve(n_free);
-        size.clear();
-        for (uint32_t seed : order) {
-            if (is_root[seed] || agg[seed] != kNone) continue;
-            const uint32_t g = (uint32_t)size.size();
-            const size_t first = disc.size();
-            disc.push_back(seed);
-            agg[seed] = g;
-            for (size_t h = first; h < disc.size() && disc.size() - first < target; ++h)
-                for (uint32_t a = ptr[disc[h]]; a < ptr[disc[h] + 1] && disc.size() - first < target; ++a) {
-                    const uint32_t o = aother[a];
-                    if (is_root[o] || agg[o] != kNone) continue;
-                    agg[o] = g;
-                    disc.push_back(o);
-                }
-            size.push_back((uint32_t)(disc.size() - first));
-        }
-        const uint32_t n0 = (uint32_t)size.size();
-        into.resize(n0);
-        std::iota(into.begin(), into.end(), 0u);
-        // small left-overs join a neighbour (their views are contiguous in disc: walk them through a start table)
-        std::vector<uint32_t> start(n0 + 1, 0);
-        for (uint32_t g = 0; g < n0; ++g) start[g + 1] = start[g] + size[g];
-        for (uint32_t g = 0; g < n0; ++g) {
-            if (size[g] >= target / 2) continue;  // (size of the aggregate as grown; one that already took others in is large enough)
-            uint32_t best = kNone;
-            for (uint32_t i = start[g]; i < start[g + 1]; ++i)
-                for (uint32_t a = ptr[disc[i]]; a < ptr[disc[i] + 1]; ++a) {
-                    const uint32_t o = aother[a];
-                    if (is_root[o]) continue;
-                    const uint32_t h = label(agg[o]);
-                    if (h == g) continue;
-                    if (best == kNone || size[h] < size[best] || (size[h] == size[best] && h < best)) best = h;
-                }
-            if (best == kNone) continue;  // a component of its own
-            into[g] = best;
-            size[best] += size[g];
-        }
-        final_id.assign(n0, kNone);
-        n_final = 0;
-        for (uint32_t g = 0; g < n0; ++g)
-            if (into[g] == g) final_id[g] = n_final++;
-        if (n_final <= kMaxAggregates - 1) break;  // (ids stay below kNoAggregate and below the 128 lanes of the coarse product)
-        if (attempt == 5 || target >= n_free) return false;
-        target *= 2;
-    }
-    for (uint32_t v = 0; v < V; ++v)
-        if (agg[v] != kNone) agg[v] = final_id[label(agg[v])];
-    // the views of every aggregate in the order they were reached (a stable counting sort of disc by aggregate)
-    std::vector<uint32_t> first_of(n_final + 1, 0);
-    for (uint32_t v : disc) ++first_of[agg[v] + 1];
-    for (uint32_t g = 0; g < n_final; ++g) first_of[g + 1] += first_of[g];
-    std::vector<uint32_t> sorted(disc.size()), fill(first_of.begin(), first_of.end() - 1);
-    for (uint32_t v : disc) sorted[fill[agg[v]]++] = v;
-    // rows: the aggregates one after the other, each padded to whole blocks; the gauge views last
-    std::vector<uint32_t> view_row(V, kNone);
-    out = TwoLevelPlan();
-    out.n_agg = n_final;
-    out.agg_block.push_back(0);
-    for (uint32_t g = 0; g < n_final; ++g) {
-        for (uint32_t i = first_of[g]; i < first_of[g + 1]; ++i) {
-            view_row[sorted[i]] = (uint32_t)out.row_view.size();
-            out.row_view.push_back(sorted[i]);
-        }
-        while (out.row_view.size() % kRowsPerBlock) out.row_view.push_back(kNone);
-        out.agg_block.push_back((uint32_t)(out.row_view.size() / kRowsPerBlock));
-    }
-    out.agg_of_block.assign(out.row_view.size() / kRowsPerBlock, kNoAggregate);
-    for (uint32_t g = 0; g < out.n_agg; ++g)
-        for (uint32_t b = out.agg_block[g]; b < out.agg_block[g + 1]; ++b) out.agg_of_block[b] = (uint8_t)g;
-    for (uint32_t v = 0; v < V; ++v)
-        if (is_root[v]) {
-            view_row[v] = (uint32_t)out.row_view.size();
-            out.row_view.push_back(v);
-        }
-    while (out.row_view.size() % kRowsPerBlock) out.row_view.push_back(kNone);
-    out.n_rows = (uint32_t)out.row_view.size();
-    out.n_blocks = out.n_rows / kRowsPerBlock;
-    out.agg_of_block.resize(out.n_blocks, kNoAggregate);
-    out.root.assign(out.n_rows, 1);
-    out.ptr.assign(out.n_rows + 1, 0);
-    out.aedge.reserve(aedge.size()); out.aother.reserve(aedge.size()); out.asign.reserve(aedge.size()); out.aagg.reserve(aedge.size());
-    for (uint32_t k = 0; k < out.n_rows; ++k) {
-        const uint32_t v = out.row_view[k];
-        if (v != kNone) {
-            out.root[k] = is_root[v];
-            for (uint32_t a = ptr[v]; a < ptr[v + 1]; ++a) {
-                const uint32_t o = aother[a];
-                out.aedge.push_back(aedge[a]);
-                out.aother.push_back(view_row[o]);
-                out.asign.push_back(asign[a]);
-                out.aagg.push_back(is_root[o] ? kNoAggregate : (uint8_t)agg[o]);
-            }
-        }
-        out.ptr[k + 1] = (uint32_t)out.aedge.size();
-    }
-    return true;
-}
+// ---- host: the solve proper.  The rotation-graph edges are already in HBM (RotEdgeDev[n_edges]); the host holds only their
+// endpoints, the initial rotations, the root flags and the spanning forest.
+//   R <- forest initialisation;  per outer step (l1_iters L1 steps, then IRLS):  residuals and robust weights;  solve the
+//   weighted-Laplacian system for the step by ONE of: the two-level PCG (deep, dense graphs), the spanning-tree PCG (sparse
+//   graphs on which Jacobi ran into its cap), the one-workgroup PCG (few views), the multi-workgroup Jacobi PCG;  R <- R exp(d);
+//   stop when the mean step falls below tol.
 
-// The solve proper.  The rotation-graph edges are already in HBM at d_rot (RotEdgeDev[n_edges]); the host holds only
-// their endpoints, the initial rotations and the root flags.
-// PGI_ROTAVG_TIMING=1: wall clock of the host-visible phases on stderr (diagnosis only)
+// The environment knobs (experiments, tests, diagnosis), read once per call.
+struct RotavgKnobs {
+    bool timing = false;                        // PGI_ROTAVG_TIMING: wall clock of the host-visible phases on stderr
+    bool trace = false;                         // PGI_ROTAVG_TRACE: one line per outer iteration on stderr
+    uint32_t single_wg_views = kSingleWgViews;  // PGI_ROTAVG_SINGLE_WG_VIEWS: at or below, the one-workgroup solve
+    uint32_t cg_iters = 0;                      // PGI_ROTAVG_CG_ITERS: replaces the parameters' iteration cap (0: not set)
+    uint32_t tree_cg_iters = 0;                 // PGI_ROTAVG_TREE_CG_ITERS: replaces the tree kernel's cap (0: not set)
+    int two_level = 1;                          // PGI_ROTAVG_TWO_LEVEL: 0 never, 1 by the depth rule, 2 always (tests)
+    double cg_tol = kInnerTolerance;            // PGI_ROTAVG_CG_TOL: relative tolerance of every inner solve
+};
+static RotavgKnobs read_rotavg_knobs() {
+    RotavgKnobs k;
+    k.timing = std::getenv("PGI_ROTAVG_TIMING") != nullptr;
+    k.trace = std::getenv("PGI_ROTAVG_TRACE") != nullptr;
+    if (const char* e = std::getenv("PGI_ROTAVG_SINGLE_WG_VIEWS")) k.single_wg_views = (uint32_t)std::max(0, std::atoi(e));
+    if (const char* e = std::getenv("PGI_ROTAVG_CG_ITERS")) k.cg_iters = (uint32_t)std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("PGI_ROTAVG_TREE_CG_ITERS")) k.tree_cg_iters = (uint32_t)std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("PGI_ROTAVG_TWO_LEVEL")) k.two_level = std::atoi(e);
+    if (const char* e = std::getenv("PGI_ROTAVG_CG_TOL")) k.cg_tol = std::min(1e-2, std::max(1e-14, std::atof(e)));
+    return k;
+}
 struct PhaseClock {
-    bool on = std::getenv("PGI_ROTAVG_TIMING") != nullptr;
+    bool on;
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    explicit PhaseClock(bool enabled) : on(enabled) {}
     void mark(const char* what) {
         if (!on) return;
         const auto now = std::chrono::steady_clock::now();
@@ -1469,473 +1035,395 @@ struct PhaseClock {
     }
 };
 
-static int rotavg_solve(pgi_ctx* ctx, const pgi_rotavg_params& prm_in, uint32_t n_views, uint32_t n_edges, const uint32_t* h_src,
-                        const uint32_t* h_dst, const RotEdgeDev* d_rot, const std::vector<double>& R,
+// The device buffers of one call (regions of one DeviceWorkspace) and what every solver of the outer loop needs.
+struct RotSolve {
+    hipStream_t st;
+    uint32_t n_views, n_edges;
+    pgi_rotavg_params prm;
+    double cg_tol;
+    double* R;
+    uint32_t *ptr, *aedge, *aother;
+    int8_t* asign;
+    uint8_t* root;
+    double *omega, *w, *diag, *x, *p, *r[2], *q[2], *s[2];
+    double *stats, *norm, *part;  // stats: mean |d|, iterations (one-workgroup solve); norm, part: block partials
+    CgState* cg;                  // two launch parities + the record the host reads
+    // tree path (views in the numbering of plan_tree_order)
+    uint32_t *tptr, *tedge, *tother, *tn2o, *tpe, *tsz, *ten, *tex;
+    int8_t* tsign;
+    TreeIncidence* inc;
+    double* its;
+    std::vector<double> norm_host;  // block partials of the step norm (multi-workgroup, tree and two-level paths)
+};
+
+// The step-norm and update launches for a solution x (row_view: see rot_update_kernel), gated on a PCG record and a veto flag or
+// not, and the copy of the norm partials.  Queued BEFORE the host looks at the record, so that a solve found converged is
+// already applied (one round trip per outer step).
+static int queue_step(RotSolve& S, uint32_t n, const double* x, const uint32_t* row_view, double* d_norm, const CgState* gate,
+                      const int* veto) {
+    const uint32_t nb = (n + kCgBlock - 1) / kCgBlock;
+    hipLaunchKernelGGL(cg_step_norm_kernel, dim3(nb), dim3(kCgBlock), 0, S.st, n, x, d_norm, gate, veto);
+    hipLaunchKernelGGL(rot_update_kernel, dim3((n + 255) / 256), dim3(256), 0, S.st, n, x, row_view, S.R, gate, veto);
+    S.norm_host.resize(3 * (size_t)nb);
+    HIP_TRY(hipMemcpyAsync(S.norm_host.data(), d_norm, S.norm_host.size() * sizeof(double), hipMemcpyDeviceToHost, S.st));
+    return 0;
+}
+
+// Which buffers a launch of cg_iteration_kernel reads and writes.  The vectors r, q, s alternate with every launch that
+// touches them; launch j reads parity (j - 1) & 1 of the partials and the state and writes parity j & 1.
+struct LaunchParity {
+    int cur = 0;          // the buffers holding the vectors of the last finished iteration
+    uint32_t launch = 0;  // launches so far
+    int prev() const { return (int)((launch + 1) & 1u); }
+    int next() const { return (int)(launch & 1u); }
+    int prev_was_init() const { return launch == 1 ? 1 : 0; }
+    void launched(int mode) {  // (a reduce-only launch, mode 2, moves nothing)
+        if (mode == 2) return;
+        cur ^= 1;
+        ++launch;
+    }
+};
+
+// Looks at the record between chunks of launches (each look a round trip): after 16, 48, 112, 176, ... launches -- except
+// that a solve whose predecessor in the outer loop converged after n iterations first runs n + 2 + n / 8 launches in one go
+// (consecutive IRLS systems differ by their weights only and need nearly the same count; launches after convergence are
+// no-ops, so WHERE the host looks changes no bit of the result), and one whose predecessor ran into the cap runs the whole
+// cap.  Graphs that may still switch to the tree path (slow_break) keep every look from 112 on: the switch is decided there.
+// solve.iterate(0): one iteration launch; iterate(2): the reduce-only launch that fills solve.record; solve.finish(record):
+// queue_step gated on the record.  Returns < 0 on a HIP error, else 1 / 0 = converged (and applied) or not; hs = the last record.
+template <class Solve>
+static int pcg_looks(Solve& solve, hipStream_t st, uint32_t cap, uint32_t& pred, bool slow_break, CgState& hs) {
+    int done = 0;
+    uint32_t ci = 0, boundary = 16, step = 16;
+    const uint32_t guess = pred + 2 + pred / 8;
+    uint32_t jump = (pred && (!slow_break || guess <= 64)) ? std::min<uint32_t>(guess, cap) : 0;
+    while (ci < cap) {
+        uint32_t target;
+        bool scheduled = true;
+        if (jump > ci) {
+            target = jump;
+            jump = 0;
+            scheduled = false;
+        } else {
+            while (boundary <= ci) {
+                step = std::min<uint32_t>(2 * step, 64);
+                boundary += step;
+            }
+            target = std::min<uint32_t>(boundary, cap);
+        }
+        for (; ci < target; ++ci) solve.iterate(0);  // kernels no-op once converged
+        solve.iterate(2);
+        {
+            const int rc = solve.finish(solve.record);
+            if (rc < 0) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(&hs, solve.record, sizeof hs, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        done = hs.done;
+        pred = done ? (uint32_t)hs.iters : cap;
+        if (done) break;
+        // hopeless for this preconditioner: after 64 iterations a well-conditioned (dense) graph has gained ten orders of
+        // magnitude, a sequence-like one not even three
+        if (scheduled && slow_break && ci >= 64) {
+            bool slow = false;
+            for (int c = 0; c < 3; ++c) slow |= hs.rz[c] > 1e-6 * hs.rz0[c];
+            if (slow) break;
+        }
+    }
+    return done;
+}
+
+// One multi-workgroup Jacobi PCG solve of the current outer step (construction queues the init kernel and the init pass).
+struct JacobiSolve {
+    RotSolve& S;
+    const uint32_t nbp;  // workgroups: kRowLanes lanes per view
+    LaunchParity lp;
+    CgState* record;     // written by the reduce-only launch, read by the host
+    explicit JacobiSolve(RotSolve& s) : S(s), nbp((s.n_views + kRowsPerBlock - 1) / kRowsPerBlock), record(s.cg + 2) {
+        hipLaunchKernelGGL(cg_init_kernel<false>, dim3(nbp), dim3(kCgBlock), 0, S.st, S.n_views, S.ptr, S.aedge, S.asign, S.root, S.omega, S.w,
+                           S.diag, S.x, S.r[0], S.p, (double*)nullptr, S.q[0], S.s[0], S.cg);
+        iterate(1);
+    }
+    void iterate(int mode) {  // 1: init pass, 0: iteration, 2: reduce the last launch's partials into `record`
+        double* const part[2] = {S.part, S.part + 6 * ((size_t)nbp + 1)};
+        const int c = lp.cur, prev = lp.prev(), next = lp.next();
+        hipLaunchKernelGGL(cg_iteration_kernel<false>, dim3(mode == 2 ? 1u : nbp), dim3(kCgBlock), 0, S.st, S.n_views, S.ptr, S.aedge, S.aother,
+                           S.root, S.w, S.diag, S.x, S.p, S.r[c], S.r[c ^ 1], S.q[c], S.q[c ^ 1], S.s[c], S.s[c ^ 1], mode, lp.prev_was_init(),
+                           S.cg_tol, part[prev], part[next], nbp, S.cg + prev, mode == 2 ? record : S.cg + next, NoCoarseLevel{});
+        lp.launched(mode);
+    }
+    int finish(const CgState* gate) { return queue_step(S, S.n_views, S.x, nullptr, S.norm, gate, nullptr); }
+};
+
+// ---- two-level preconditioner (see "two-level PCG" above).  WHEN: the graph is too dense for the tree path, too large for
+// the one-workgroup solve, and DEEP -- the breadth-first walk from the gauge views needs kTwoLevelDepth levels or more, as on a
+// walk or a ring (V / reach levels), where Jacobi needs hundreds of iterations whatever the weights; a densely connected
+// graph has a handful of levels, Jacobi converges in ~20 iterations there and a capped first L1 solve is merely a hard
+// first step.
+constexpr uint32_t kTwoLevelDepth = 12;
+struct TwoLevel {  // the plan and its device buffers (a workspace of their own: most graphs never need them)
+    TwoLevelPlan plan;
+    DeviceWorkspace ws;
+    uint32_t *ptr, *edge, *other, *row_view, *agg_block;
+    int8_t* sign;
+    uint8_t *agg, *root, *agg_of_block;
+    double *diag, *x, *p, *r[2], *q[2], *s[2], *part, *rpart, *cs, *Ac, *Ainv, *norm;
+    CgState* cg;
+    int* status;  // set: the coarse matrix was not inverted
+    size_t inv_lds = 0;
+};
+// 0: ready; 1: this graph cannot have a plan; < 0: error
+static int plan_and_upload_two_level(RotSolve& S, const IncidenceCsr& g, const std::vector<uint8_t>& is_root,
+                                     const std::vector<uint32_t>& bfs_order, TwoLevel& t) {
+    if (!plan_two_level(S.n_views, g, is_root, bfs_order, kRowsPerBlock, kMaxAggregates, t.plan)) return 1;
+    const TwoLevelPlan& pl = t.plan;
+    const size_t N = pl.n_rows, NB = pl.n_blocks, NA = pl.n_agg, I = pl.aedge.size();
+    t.ws.add(t.ptr, N + 1); t.ws.add(t.edge, I); t.ws.add(t.other, I); t.ws.add(t.sign, I); t.ws.add(t.agg, I);
+    t.ws.add(t.root, N); t.ws.add(t.row_view, N); t.ws.add(t.agg_block, NA + 1); t.ws.add(t.agg_of_block, NB);
+    t.ws.add(t.diag, N); t.ws.add(t.x, 3 * N); t.ws.add(t.p, 3 * N);
+    for (int b = 0; b < 2; ++b) { t.ws.add(t.r[b], 3 * N); t.ws.add(t.q[b], 3 * N); t.ws.add(t.s[b], 3 * N); }
+    t.ws.add(t.part, 2 * 9 * (NB + 1));  // block partials, by launch parity
+    t.ws.add(t.rpart, 3 * NB); t.ws.add(t.cs, 2 * 9 * NA); t.ws.add(t.Ac, NA * NA); t.ws.add(t.Ainv, NA * NA);
+    t.ws.add(t.cg, 4); t.ws.add(t.status, 4); t.ws.add(t.norm, 3 * ((N + kCgBlock - 1) / kCgBlock));
+    HIP_TRY(t.ws.alloc());
+    HIP_TRY(upload(t.ptr, pl.ptr, S.st));
+    HIP_TRY(upload(t.edge, pl.aedge, S.st));
+    HIP_TRY(upload(t.other, pl.aother, S.st));
+    HIP_TRY(upload(t.sign, pl.asign, S.st));
+    HIP_TRY(upload(t.agg, pl.aagg, S.st));
+    HIP_TRY(upload(t.root, pl.root, S.st));
+    HIP_TRY(upload(t.row_view, pl.row_view, S.st));
+    HIP_TRY(upload(t.agg_block, pl.agg_block, S.st));
+    HIP_TRY(upload(t.agg_of_block, pl.agg_of_block, S.st));
+    HIP_TRY(hipStreamSynchronize(S.st));
+    t.inv_lds = NA * NA * sizeof(double);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&cg2_coarse_invert_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)t.inv_lds));
+    return 0;
+}
+// One two-level solve of the current outer step (construction queues the init kernel, the coarse matrix and the init pass).
+struct TwoLevelSolve {
+    RotSolve& S;
+    TwoLevel& t;
+    const uint32_t N, NB, NA;
+    LaunchParity lp;
+    CgState* record;
+    int status = 0;  // host copy of t.status, valid after the synchronisation that follows a finish()
+    TwoLevelSolve(RotSolve& s, TwoLevel& two) : S(s), t(two), N(two.plan.n_rows), NB(two.plan.n_blocks), NA(two.plan.n_agg), record(two.cg + 2) {
+        hipLaunchKernelGGL(cg_init_kernel<true>, dim3(NB), dim3(kCgBlock), 0, S.st, N, t.ptr, t.edge, t.sign, t.root, S.omega, S.w, t.diag, t.x,
+                           t.r[0], t.p, t.rpart, t.q[0], t.s[0], t.cg);
+        hipLaunchKernelGGL(cg2_coarse_assemble_kernel, dim3(NA), dim3(kMaxAggregates * kAsmSegments), 0, S.st, NA, t.agg_block, t.ptr, t.edge, t.agg,
+                           t.root, S.w, t.diag, t.Ac);
+        hipLaunchKernelGGL(cg2_coarse_invert_kernel, dim3(1), dim3(1024), t.inv_lds, S.st, NA, t.Ac, t.Ainv, t.status);
+        iterate(1);
+    }
+    void iterate(int mode) {
+        double* const part[2] = {t.part, t.part + 9 * ((size_t)NB + 1)};
+        double* const cs[2] = {t.cs, t.cs + 9 * (size_t)NA};
+        const int c = lp.cur, prev = lp.prev(), next = lp.next();
+        const CoarseLevel coarse{NA, t.agg, t.agg_block, t.agg_of_block, t.Ainv, t.rpart, cs[prev], cs[next]};
+        hipLaunchKernelGGL(cg_iteration_kernel<true>, dim3(mode == 2 ? 1u : NB), dim3(kCgBlock), 0, S.st, N, t.ptr, t.edge, t.other, t.root, S.w,
+                           t.diag, t.x, t.p, t.r[c], t.r[c ^ 1], t.q[c], t.q[c ^ 1], t.s[c], t.s[c ^ 1], mode, lp.prev_was_init(), S.cg_tol,
+                           part[prev], part[next], NB, t.cg + prev, mode == 2 ? record : t.cg + next, coarse);
+        lp.launched(mode);
+    }
+    int finish(const CgState* gate) {
+        const int rc = queue_step(S, N, t.x, t.row_view, t.norm, gate, t.status);
+        if (rc < 0) return rc;
+        HIP_TRY(hipMemcpyAsync(&status, t.status, sizeof status, hipMemcpyDeviceToHost, S.st));
+        return 0;
+    }
+};
+// applied to the rotations, S.norm_host filled, iters = PCG iterations; 1 when the coarse matrix could not be inverted (nothing
+// was applied, the caller falls back), < 0 on a HIP error
+static int solve_two_level(RotSolve& S, TwoLevel& t, uint32_t& predicted, double& iters) {
+    TwoLevelSolve solve(S, t);
+    CgState hs{};
+    const int done = pcg_looks(solve, S.st, S.prm.cg_iters, predicted, false, hs);
+    if (done < 0) return done;
+    if (!done) {  // ran into the cap: the truncated solution is the step
+        const int rc = solve.finish(nullptr);
+        if (rc < 0) return rc;
+        HIP_TRY(hipStreamSynchronize(S.st));
+    }
+    if (solve.status) return 1;
+    iters = hs.iters;
+    return 0;
+}
+
+// ---- tree path (rot_solve_tree_kernel).  Only sparse graphs qualify: the forest holds V - 1 of the E edges, and on a dense
+// graph (E / V = 21 in the k = 20 benchmark) it is a far worse preconditioner than Jacobi (1 380 iterations against 19) -- there
+// a capped first L1 solve is simply a hard first step, not a reason to switch.
+struct TreePath {
+    bool ok = false;          // the graph qualifies
+    bool in_use = false;      // set once the Jacobi-preconditioned solve has run into its iteration cap
+    uint32_t own = 0;         // views per thread
+    uint32_t cg_iters = 0;    // iteration cap of the kernel
+    size_t lds = 0;
+    TreeOrder order;          // (kept: the uploads read it)
+};
+static void solve_with_tree(RotSolve& S, const TreePath& tp) {  // writes every entry of x
+    hipLaunchKernelGGL(rot_solve_tree_kernel, dim3(3), dim3(1024), tp.lds, S.st, S.n_views, tp.own, S.tptr, S.tedge, S.tother, S.tsign, S.tpe,
+                       S.tsz, S.ten, S.tex, S.tn2o, S.omega, S.w, tp.cg_iters, S.cg_tol, S.inc, S.x, S.its);
+}
+
+// Allocation and uploads: the adjacency, the initial rotations, the root flags, and for a graph that qualifies the tree order.
+static int rotavg_setup(RotSolve& S, DeviceWorkspace& ws, const IncidenceCsr& g, const std::vector<double>& R,
+                        const std::vector<uint8_t>& is_root, const std::vector<std::vector<ForestEdge>>& forest, TreePath& tp) {
+    const size_t V = S.n_views, E = S.n_edges;
+    ws.add(S.R, 9 * V); ws.add(S.ptr, V + 1); ws.add(S.aedge, 2 * E); ws.add(S.aother, 2 * E); ws.add(S.asign, 2 * E); ws.add(S.root, V);
+    ws.add(S.omega, 3 * E); ws.add(S.w, E); ws.add(S.diag, V); ws.add(S.x, 3 * V); ws.add(S.p, 3 * V);
+    for (int b = 0; b < 2; ++b) { ws.add(S.r[b], 3 * V); ws.add(S.q[b], 3 * V); ws.add(S.s[b], 3 * V); }
+    ws.add(S.stats, 2); ws.add(S.norm, 3 * ((V + kCgBlock - 1) / kCgBlock)); ws.add(S.cg, 4);
+    ws.add(S.part, 2 * 6 * ((V + kRowsPerBlock - 1) / kRowsPerBlock + 1));  // block partials, by launch parity
+    ws.add(S.tptr, V + 1); ws.add(S.tedge, 2 * E); ws.add(S.tother, 2 * E); ws.add(S.tsign, 2 * E);
+    ws.add(S.tn2o, V); ws.add(S.tpe, V); ws.add(S.tsz, V); ws.add(S.ten, V); ws.add(S.tex, V); ws.add(S.inc, 2 * E); ws.add(S.its, 4);
+    HIP_TRY(ws.alloc());
+    HIP_TRY(upload(S.R, R, S.st));
+    HIP_TRY(upload(S.ptr, g.ptr, S.st));
+    HIP_TRY(upload(S.aedge, g.edge, S.st));
+    HIP_TRY(upload(S.aother, g.other, S.st));
+    HIP_TRY(upload(S.asign, g.sign, S.st));
+    HIP_TRY(upload(S.root, is_root, S.st));
+    tp.ok = S.n_views <= kTreeViews && (uint64_t)S.n_edges <= 8ull * S.n_views;
+    if (!tp.ok) return 0;
+    tp.own = std::max<uint32_t>(1u, (S.n_views + 1023u) / 1024u);
+    tp.order = plan_tree_order(S.n_views, g, is_root, forest);
+    const TreeOrder& t = tp.order;
+    HIP_TRY(upload(S.tptr, t.adj.ptr, S.st));
+    HIP_TRY(upload(S.tedge, t.adj.edge, S.st));
+    HIP_TRY(upload(S.tother, t.adj.other, S.st));
+    HIP_TRY(upload(S.tsign, t.adj.sign, S.st));
+    HIP_TRY(upload(S.tn2o, t.new_to_old, S.st));
+    HIP_TRY(upload(S.tpe, t.parent_edge, S.st));
+    HIP_TRY(upload(S.tsz, t.sub_size, S.st));
+    HIP_TRY(upload(S.ten, t.tour_enter, S.st));
+    HIP_TRY(upload(S.tex, t.tour_exit, S.st));
+    tp.lds = ((size_t)3 * 1024 * tp.own + 16) * sizeof(double);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&rot_solve_tree_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds));
+    return 0;
+}
+
+static int rotavg_solve(pgi_ctx* ctx, const RotavgKnobs& knobs, const pgi_rotavg_params& prm_in, uint32_t n_views, uint32_t n_edges,
+                        const uint32_t* h_src, const uint32_t* h_dst, const RotEdgeDev* d_rot, const std::vector<double>& R,
                         const std::vector<uint8_t>& is_root, const std::vector<std::vector<ForestEdge>>& forest, double* h_R_out,
                         uint32_t* h_iters_out) {
-    PhaseClock clk;
-    // CSR adjacency, incidences in edge order
-    std::vector<uint32_t> ptr(n_views + 1, 0), aedge(2 * (size_t)n_edges), aother(2 * (size_t)n_edges);
-    std::vector<int8_t> asign(2 * (size_t)n_edges);
-    for (uint32_t e = 0; e < n_edges; ++e) {
-        ++ptr[h_src[e] + 1];
-        ++ptr[h_dst[e] + 1];
-    }
-    for (uint32_t k = 0; k < n_views; ++k) ptr[k + 1] += ptr[k];
+    PhaseClock clk(knobs.timing);
+    const IncidenceCsr g = build_incidence_csr(n_views, n_edges, h_src, h_dst, -1);  // sign +1: the view is the edge's dst
+    RotSolve S{};
+    S.st = ctx->stream;
+    S.n_views = n_views;
+    S.n_edges = n_edges;
+    S.prm = prm_in;
+    if (knobs.cg_iters) S.prm.cg_iters = knobs.cg_iters;
+    S.cg_tol = knobs.cg_tol;
+    const pgi_rotavg_params& prm = S.prm;
+    hipStream_t st = S.st;
+    DeviceWorkspace ws;
+    TreePath tree;
     {
-        std::vector<uint32_t> fill(ptr.begin(), ptr.end() - 1);
-        for (uint32_t e = 0; e < n_edges; ++e) {
-            uint32_t a = fill[h_src[e]]++;
-            aedge[a] = e; aother[a] = h_dst[e]; asign[a] = -1;
-            a = fill[h_dst[e]]++;
-            aedge[a] = e; aother[a] = h_src[e]; asign[a] = +1;
-        }
+        const int rc = rotavg_setup(S, ws, g, R, is_root, forest, tree);
+        if (rc < 0) return rc;
     }
-    const size_t V = n_views, E = n_edges;
-    // Tree path (rot_solve_tree_kernel): views renumbered in depth-first preorder of the spanning forest, with subtree
-    // sizes, the edge to the parent and the Euler-tour positions; the adjacency again in that numbering.
-    // Only sparse graphs qualify: the forest holds V - 1 of the E edges, and on a dense graph (E / V = 21 in the k = 20
-    // benchmark) it is a far worse preconditioner than Jacobi (1 380 iterations against 19) -- there a capped first L1
-    // solve is simply a hard first step, not a reason to switch.
-    const bool tree_ok = n_views <= kTreeViews && (uint64_t)n_edges <= 8ull * n_views;
-    const uint32_t own = tree_ok ? std::max<uint32_t>(1u, (n_views + 1023u) / 1024u) : 0u;
-    std::vector<uint32_t> t_n2o, t_pedge, t_size, t_enter, t_exit, t_ptr, t_edge, t_other;
-    std::vector<int8_t> t_sign;
-    if (tree_ok) {
-        std::vector<uint32_t> o2n(V, 0xFFFFFFFFu);
-        t_n2o.reserve(V); t_pedge.assign(V, 0xFFFFFFFFu); t_size.assign(V, 1u); t_enter.assign(V, 0u); t_exit.assign(V, 0u);
-        uint32_t clock = 0;
-        struct Frame { uint32_t v, next; };
-        std::vector<Frame> stack;
-        for (uint32_t root = 0; root < n_views; ++root) {
-            if (!is_root[root]) continue;
-            o2n[root] = (uint32_t)t_n2o.size();
-            t_n2o.push_back(root);
-            t_enter[o2n[root]] = clock++;
-            stack.assign(1, Frame{root, 0u});
-            while (!stack.empty()) {
-                Frame& f = stack.back();
-                if (f.next < forest[f.v].size()) {
-                    const ForestEdge& pr = forest[f.v][f.next++];
-                    const uint32_t c = pr.other & 0x7FFFFFFFu;
-                    if (o2n[c] != 0xFFFFFFFFu) continue;  // the parent
-                    o2n[c] = (uint32_t)t_n2o.size();
-                    t_n2o.push_back(c);
-                    t_pedge[o2n[c]] = pr.edge;
-                    t_enter[o2n[c]] = clock++;
-                    stack.push_back(Frame{c, 0u});
-                } else {
-                    const uint32_t k = o2n[f.v];
-                    t_size[k] = (uint32_t)t_n2o.size() - k;
-                    t_exit[k] = clock++;
-                    stack.pop_back();
-                }
-            }
-        }
-        t_ptr.assign(V + 1, 0); t_edge.resize(2 * E); t_other.resize(2 * E); t_sign.resize(2 * E);
-        for (uint32_t k = 0; k < n_views; ++k) {
-            const uint32_t u = t_n2o[k];
-            uint32_t o = t_ptr[k];
-            for (uint32_t a = ptr[u]; a < ptr[u + 1]; ++a, ++o) {
-                t_edge[o] = aedge[a];
-                t_other[o] = o2n[aother[a]];
-                t_sign[o] = asign[a];
-            }
-            t_ptr[k + 1] = o;
-        }
-    }
-    // one allocation, carved
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_R = carve(V * 72), o_ptr = carve((V + 1) * 4),
-                 o_aedge = carve(2 * E * 4), o_aother = carve(2 * E * 4), o_asign = carve(2 * E),
-                 o_root = carve(V), o_omega = carve(E * 24), o_w = carve(E * 8), o_diag = carve(V * 8),
-                 o_x = carve(V * 24), o_r = carve(V * 24), o_p = carve(V * 24), o_Ap = carve(V * 24), o_r2 = carve(V * 24), o_q2 = carve(V * 24), o_s = carve(V * 24),
-                 o_s2 = carve(V * 24),
-                 o_stats = carve(16), o_norm = carve(3 * 8 * ((V + kCgBlock - 1) / kCgBlock)), o_cg = carve(4 * sizeof(CgState)),  // two launch parities + the record the host reads
-                 o_part = carve(2 * 6 * 8 * ((V + kRowsPerBlock - 1) / kRowsPerBlock + 1)),  // block partials, by launch parity
-                 // tree path
-                 o_tptr = carve((V + 1) * 4), o_tedge = carve(2 * E * 4), o_tother = carve(2 * E * 4), o_tsign = carve(2 * E),
-                 o_tn2o = carve(V * 4), o_tpe = carve(V * 4), o_tsz = carve(V * 4), o_ten = carve(V * 4), o_tex = carve(V * 4),
-                 o_aw = carve(2 * E * sizeof(TreeIncidence)), o_its = carve(32);
-    char* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, off));
-    struct Guard {
-        char* p;
-        ~Guard() { (void)hipFree(p); }
-    } guard{d};
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_R, R.data(), V * 72, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_ptr, ptr.data(), (V + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_aedge, aedge.data(), 2 * E * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_aother, aother.data(), 2 * E * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_asign, asign.data(), 2 * E, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_root, is_root.data(), V, hipMemcpyHostToDevice, st));
-    size_t tree_lds = 0;
-    if (tree_ok) {
-        HIP_TRY(hipMemcpyAsync(d + o_tptr, t_ptr.data(), (V + 1) * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d + o_tedge, t_edge.data(), 2 * E * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d + o_tother, t_other.data(), 2 * E * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d + o_tsign, t_sign.data(), 2 * E, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d + o_tn2o, t_n2o.data(), V * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d + o_tpe, t_pedge.data(), V * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d + o_tsz, t_size.data(), V * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d + o_ten, t_enter.data(), V * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d + o_tex, t_exit.data(), V * 4, hipMemcpyHostToDevice, st));
-        tree_lds = ((size_t)3 * 1024 * own + 16) * 8;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&rot_solve_tree_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)tree_lds));
-    }
+    tree.cg_iters = knobs.tree_cg_iters ? knobs.tree_cg_iters : std::max<uint32_t>(prm.cg_iters, 1000u);
     if (clk.on) (void)hipStreamSynchronize(st);
     clk.mark("solve: adjacency, allocation, uploads");
-    bool use_tree = false;  // set once the Jacobi-preconditioned solve has run into its iteration cap
-    uint32_t single_wg_views = kSingleWgViews;
-    if (const char* e = std::getenv("PGI_ROTAVG_SINGLE_WG_VIEWS")) single_wg_views = (uint32_t)std::max(0, std::atoi(e));  // experiments
-    const bool trace = std::getenv("PGI_ROTAVG_TRACE") != nullptr;
-    pgi_rotavg_params prm = prm_in;
-    if (const char* e = std::getenv("PGI_ROTAVG_CG_ITERS")) prm.cg_iters = (uint32_t)std::max(1, std::atoi(e));  // experiments
-    // iteration cap of the tree-preconditioned kernel; PGI_ROTAVG_TREE_CG_ITERS replaces it (tests: a fixed number of steps)
-    uint32_t tree_cg_iters = std::max<uint32_t>(prm.cg_iters, 1000u);
-    if (const char* e = std::getenv("PGI_ROTAVG_TREE_CG_ITERS")) tree_cg_iters = (uint32_t)std::max(1, std::atoi(e));  // experiments
-    const double sigma = prm.sigma_deg * 3.14159265358979323846 / 180.0;
-    uint32_t iters = 0;
-    uint32_t predicted = 0;   // PCG iterations of the previous outer step's solve (multi-workgroup Jacobi branch)
-    uint32_t predicted2 = 0;  // the same for the two-level solves
 
-    // Looks at the record between chunks of launches (each look a round trip): after 16, 48, 112, 176, ... launches -- except
-    // that a solve whose predecessor in the outer loop converged after n iterations first runs n + 2 + n / 8 launches in one go
-    // (consecutive IRLS systems differ by their weights only and need nearly the same count; launches after convergence are
-    // no-ops, so WHERE the host looks changes no bit of the result), and one whose predecessor ran into the cap runs the whole
-    // cap.  Graphs that may still switch to the tree path keep every look from 112 on: the switch is decided there.
-    // iterate(0): one iteration launch; iterate(2): the reduce-only launch that fills `record`; finish(record): the step-norm and
-    // update launches gated on the record, and the copy of the norm partials -- queued before the host looks, so that a solve
-    // found converged is already applied (one round trip per outer step).  Returns < 0 on a HIP error, else 1 / 0 = converged
-    // (and applied) or not; hs = the last record.
-    auto pcg_looks = [&](auto&& iterate, auto&& finish, const CgState* record, uint32_t cap, uint32_t& pred, bool slow_break, CgState& hs) -> int {
-        int done = 0;
-        uint32_t ci = 0, boundary = 16, step = 16;
-        const uint32_t guess = pred + 2 + pred / 8;
-        uint32_t jump = (pred && (!slow_break || guess <= 64)) ? std::min<uint32_t>(guess, cap) : 0;
-        while (ci < cap) {
-            uint32_t target;
-            bool scheduled = true;
-            if (jump > ci) {
-                target = jump;
-                jump = 0;
-                scheduled = false;
-            } else {
-                while (boundary <= ci) {
-                    step = std::min<uint32_t>(2 * step, 64);
-                    boundary += step;
-                }
-                target = std::min<uint32_t>(boundary, cap);
-            }
-            for (; ci < target; ++ci) iterate(0);  // kernels no-op once converged
-            iterate(2);
-            {
-                const int rc = finish(record);
-                if (rc < 0) return rc;
-            }
-            HIP_TRY(hipMemcpyAsync(&hs, record, sizeof hs, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            done = hs.done;
-            pred = done ? (uint32_t)hs.iters : cap;
-            if (done) break;
-            // hopeless for this preconditioner: after 64 iterations a well-conditioned (dense) graph has gained ten orders of
-            // magnitude, a sequence-like one not even three
-            if (scheduled && slow_break && ci >= 64) {
-                bool slow = false;
-                for (int c = 0; c < 3; ++c) slow |= hs.rz[c] > 1e-6 * hs.rz0[c];
-                if (slow) break;
-            }
-        }
-        return done;
-    };
-
-    // ---- two-level preconditioner (see cg2_iteration_kernel).  WHEN: the graph is too dense for the tree path, too large for
-    // the one-workgroup solve, and DEEP -- the breadth-first walk from the gauge views needs kTwoLevelDepth levels or more, as on a
-    // walk or a ring (V / reach levels), where Jacobi needs hundreds of iterations whatever the weights; a densely connected
-    // graph has a handful of levels, Jacobi converges in ~20 iterations there and a capped first L1 solve is merely a hard
-    // first step.  PGI_ROTAVG_TWO_LEVEL: 0 never, 1 (default) by that rule, 2 always (tests).
-    constexpr uint32_t kTwoLevelDepth = 12;
-    const char* two_env = std::getenv("PGI_ROTAVG_TWO_LEVEL");
-    const int two_mode = two_env ? std::atoi(two_env) : 1;
+    TwoLevel two;
     bool use_two = false;
-    TwoLevelPlan plan;
-    struct Guard2 {
-        char* p = nullptr;
-        ~Guard2() { if (p) (void)hipFree(p); }
-    } guard2;
-    size_t t_ptr2 = 0, t_edge2 = 0, t_other2 = 0, t_sign2 = 0, t_agg2 = 0, t_root2 = 0, t_view2 = 0, t_ablk2 = 0, t_aob2 = 0, t_diag2 = 0, t_x2 = 0,
-           t_p2 = 0, t_r2[2] = {0, 0}, t_q2[2] = {0, 0}, t_s2[2] = {0, 0}, t_part2 = 0, t_rpart2 = 0, t_cs2 = 0, t_Ac2 = 0, t_Ainv2 = 0, t_cg2 = 0,
-           t_status2 = 0, t_norm2 = 0;
-    size_t inv_lds = 0;
-    std::vector<uint32_t> bfs_order;
-    auto ensure_plan = [&]() -> int {  // 0: ready; 1: this graph cannot have one; < 0: error
-        if (guard2.p) return 0;
-        if (!plan_two_level(n_views, ptr, aedge, aother, asign, is_root, bfs_order, plan)) return 1;
-        const size_t N = plan.n_rows, NB = plan.n_blocks, NA = plan.n_agg, I = plan.aedge.size();
-        size_t o2 = 0;
-        auto carve2 = [&](size_t bytes) {
-            const size_t o = o2;
-            o2 += (bytes + 255) & ~(size_t)255;
-            return o;
-        };
-        t_ptr2 = carve2((N + 1) * 4); t_edge2 = carve2(I * 4); t_other2 = carve2(I * 4); t_sign2 = carve2(I); t_agg2 = carve2(I);
-        t_root2 = carve2(N); t_view2 = carve2(N * 4); t_ablk2 = carve2((NA + 1) * 4); t_aob2 = carve2(NB); t_diag2 = carve2(N * 8);
-        t_x2 = carve2(N * 24); t_p2 = carve2(N * 24);
-        for (int b = 0; b < 2; ++b) { t_r2[b] = carve2(N * 24); t_q2[b] = carve2(N * 24); t_s2[b] = carve2(N * 24); }
-        t_part2 = carve2(2 * 9 * 8 * (NB + 1)); t_rpart2 = carve2(3 * 8 * NB); t_cs2 = carve2(2 * 9 * 8 * NA); t_Ac2 = carve2(NA * NA * 8);
-        t_Ainv2 = carve2(NA * NA * 8); t_cg2 = carve2(4 * sizeof(CgState)); t_status2 = carve2(16);
-        t_norm2 = carve2(3 * 8 * ((N + kCgBlock - 1) / kCgBlock));
-        HIP_TRY(hipMalloc((void**)&guard2.p, o2));
-        char* d2 = guard2.p;
-        HIP_TRY(hipMemcpyAsync(d2 + t_ptr2, plan.ptr.data(), (N + 1) * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d2 + t_edge2, plan.aedge.data(), I * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d2 + t_other2, plan.aother.data(), I * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d2 + t_sign2, plan.asign.data(), I, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d2 + t_agg2, plan.aagg.data(), I, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d2 + t_root2, plan.root.data(), N, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d2 + t_view2, plan.row_view.data(), N * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d2 + t_ablk2, plan.agg_block.data(), (NA + 1) * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d2 + t_aob2, plan.agg_of_block.data(), NB, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));  // (the plan's vectors are read by the copies)
-        inv_lds = NA * NA * 8;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&cg2_coarse_invert_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)inv_lds));
-        return 0;
-    };
-    // relative tolerance of every inner solve (kInnerTolerance above; PGI_ROTAVG_CG_TOL overrides)
-    double cg_tol = kInnerTolerance;
-    if (const char* e = std::getenv("PGI_ROTAVG_CG_TOL")) cg_tol = std::min(1e-2, std::max(1e-14, std::atof(e)));
-    double two_iters = 0;  // iterations of the last two-level solve (trace)
-    std::vector<double> norm_host;  // block partials of the step norm (multi-workgroup, tree and two-level paths)
-    // one two-level solve of the current outer step, applied to the rotations, norm_host filled; 1 when the coarse matrix could
-    // not be inverted (nothing was applied, the caller falls back), < 0 on a HIP error
-    auto solve_two_level = [&]() -> int {
-        char* d2 = guard2.p;
-        const uint32_t N = plan.n_rows, NB = plan.n_blocks, NA = plan.n_agg;
-        const uint32_t* ptr2 = (const uint32_t*)(d2 + t_ptr2);
-        const uint32_t* edge2 = (const uint32_t*)(d2 + t_edge2);
-        const uint32_t* other2 = (const uint32_t*)(d2 + t_other2);
-        const uint8_t* agg2 = (const uint8_t*)(d2 + t_agg2);
-        const uint8_t* root2 = (const uint8_t*)(d2 + t_root2);
-        double* diag2 = (double*)(d2 + t_diag2);
-        double* x2 = (double*)(d2 + t_x2);
-        double* p2 = (double*)(d2 + t_p2);
-        double* rbuf[2] = {(double*)(d2 + t_r2[0]), (double*)(d2 + t_r2[1])};
-        double* qbuf[2] = {(double*)(d2 + t_q2[0]), (double*)(d2 + t_q2[1])};
-        double* sbuf[2] = {(double*)(d2 + t_s2[0]), (double*)(d2 + t_s2[1])};
-        double* part = (double*)(d2 + t_part2);
-        double* pbuf[2] = {part, part + 9 * ((size_t)NB + 1)};
-        double* cs = (double*)(d2 + t_cs2);
-        double* csbuf[2] = {cs, cs + 9 * (size_t)NA};
-        CgState* cst = (CgState*)(d2 + t_cg2);
-        CgState* record = cst + 2;
-        hipLaunchKernelGGL(cg2_init_kernel, dim3(NB), dim3(kCgBlock), 0, st, N, ptr2, edge2, (const int8_t*)(d2 + t_sign2), root2,
-                           (const double*)(d + o_omega), (const double*)(d + o_w), diag2, x2, rbuf[0], p2, (double*)(d2 + t_rpart2), qbuf[0], sbuf[0], cst);
-        hipLaunchKernelGGL(cg2_coarse_assemble_kernel, dim3(NA), dim3(kMaxAggregates * kAsmSegments), 0, st, NA, (const uint32_t*)(d2 + t_ablk2), ptr2, edge2,
-                           agg2, root2, (const double*)(d + o_w), (const double*)diag2, (double*)(d2 + t_Ac2));
-        hipLaunchKernelGGL(cg2_coarse_invert_kernel, dim3(1), dim3(1024), inv_lds, st, NA, (const double*)(d2 + t_Ac2), (double*)(d2 + t_Ainv2),
-                           (int*)(d2 + t_status2));
-        int cur = 0;
-        uint32_t launch = 0;
-        auto iterate = [&](int mode) {
-            const int prev = (int)((launch + 1) & 1u), next = (int)(launch & 1u);
-            hipLaunchKernelGGL(cg2_iteration_kernel, dim3(mode == 2 ? 1u : NB), dim3(kCgBlock), 0, st, N, ptr2, edge2, other2, agg2, root2,
-                               (const double*)(d + o_w), (const double*)diag2, x2, p2, (const double*)rbuf[cur], rbuf[cur ^ 1],
-                               (const double*)qbuf[cur], qbuf[cur ^ 1], (const double*)sbuf[cur], sbuf[cur ^ 1], mode, launch == 1 ? 1 : 0, cg_tol,
-                               (const double*)pbuf[prev], pbuf[next], NB, (const CgState*)(cst + prev), mode == 2 ? record : cst + next, NA,
-                               (const uint32_t*)(d2 + t_ablk2), (const uint8_t*)(d2 + t_aob2), (const double*)(d2 + t_Ainv2),
-                               (const double*)(d2 + t_rpart2), (const double*)csbuf[prev], csbuf[next]);
-            if (mode != 2) {
-                cur ^= 1;
-                ++launch;
-            }
-        };
-        int status = 0;
-        const int* veto = (const int*)(d2 + t_status2);
-        auto finish = [&](const CgState* gate) -> int {
-            const uint32_t nbn = (N + kCgBlock - 1) / kCgBlock;
-            hipLaunchKernelGGL(cg_step_norm_kernel, dim3(nbn), dim3(kCgBlock), 0, st, N, (const double*)x2, (double*)(d2 + t_norm2), gate, veto);
-            hipLaunchKernelGGL(rot_update_rows_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, (const double*)x2,
-                               (const uint32_t*)(d2 + t_view2), (double*)(d + o_R), gate, veto);
-            norm_host.resize(3 * (size_t)nbn);
-            HIP_TRY(hipMemcpyAsync(norm_host.data(), d2 + t_norm2, norm_host.size() * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(&status, d2 + t_status2, sizeof status, hipMemcpyDeviceToHost, st));
-            return 0;
-        };
-        iterate(1);
-        CgState hs{};
-        const int done = pcg_looks(iterate, finish, record, prm.cg_iters, predicted2, false, hs);
-        if (done < 0) return done;
-        if (!done) {  // ran into the cap: the truncated solution is the step
-            const int rc = finish(nullptr);
-            if (rc < 0) return rc;
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        if (status) return 1;
-        two_iters = hs.iters;
-        return 0;
-    };
-    if (two_mode == 2 || (two_mode == 1 && !tree_ok && n_views > single_wg_views)) {
-        const uint32_t depth = bfs_from_gauge_views(n_views, ptr, aother, is_root, bfs_order);
-        if (two_mode == 2 || depth >= kTwoLevelDepth) {
-            const int rc = ensure_plan();
+    if (knobs.two_level == 2 || (knobs.two_level == 1 && !tree.ok && n_views > knobs.single_wg_views)) {
+        std::vector<uint32_t> bfs_order;
+        const uint32_t depth = bfs_from_gauge_views(n_views, g, is_root, bfs_order);
+        if (knobs.two_level == 2 || depth >= kTwoLevelDepth) {
+            const int rc = plan_and_upload_two_level(S, g, is_root, bfs_order, two);
             if (rc < 0) return rc;
             use_two = rc == 0;
         }
         if (clk.on) std::fprintf(stderr, "[rotavg timing] breadth-first depth %u, two-level %s (%u aggregates, %u rows)\n", depth, use_two ? "on" : "off",
-                                 plan.n_agg, plan.n_rows);
+                                 two.plan.n_agg, two.plan.n_rows);
         clk.mark("solve: two-level plan");
     }
 
+    const double sigma = prm.sigma_deg * 3.14159265358979323846 / 180.0;
+    uint32_t iters = 0;
+    uint32_t predicted = 0, predicted2 = 0;  // PCG iterations of the previous outer step's solve: Jacobi, two-level
     for (uint32_t it = 0; it < prm.l1_iters + prm.irls_iters; ++it) {
-        hipLaunchKernelGGL(rot_residual_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, st, d_rot, n_edges,
-                           (const double*)(d + o_R), it < prm.l1_iters ? 1 : 0, sigma, (double*)(d + o_omega), (double*)(d + o_w));
-        // step norm and update of a solution in view numbering (x), gated on a PCG record or not
-        auto finish_views = [&](const CgState* gate) -> int {
-            const uint32_t nb = (n_views + kCgBlock - 1) / kCgBlock;
-            hipLaunchKernelGGL(cg_step_norm_kernel, dim3(nb), dim3(kCgBlock), 0, st, n_views, (const double*)(d + o_x), (double*)(d + o_norm), gate,
-                               (const int*)nullptr);
-            hipLaunchKernelGGL(rot_update_kernel, dim3((n_views + 255) / 256), dim3(256), 0, st, n_views, (const double*)(d + o_x),
-                               (double*)(d + o_R), gate, (const int*)nullptr);
-            norm_host.resize(3 * (size_t)nb);
-            HIP_TRY(hipMemcpyAsync(norm_host.data(), d + o_norm, norm_host.size() * 8, hipMemcpyDeviceToHost, st));
-            return 0;
-        };
-        auto solve_with_tree = [&]() {  // writes every entry of x
-            hipLaunchKernelGGL(rot_solve_tree_kernel, dim3(3), dim3(1024), tree_lds, st, n_views, own, (const uint32_t*)(d + o_tptr),
-                               (const uint32_t*)(d + o_tedge), (const uint32_t*)(d + o_tother), (const int8_t*)(d + o_tsign),
-                               (const uint32_t*)(d + o_tpe), (const uint32_t*)(d + o_tsz), (const uint32_t*)(d + o_ten),
-                               (const uint32_t*)(d + o_tex), (const uint32_t*)(d + o_tn2o), (const double*)(d + o_omega),
-                               (const double*)(d + o_w), tree_cg_iters, cg_tol, (TreeIncidence*)(d + o_aw),
-                               (double*)(d + o_x), (double*)(d + o_its));
-        };
-        // multi-workgroup Jacobi PCG: 1 = converged (and applied: finish_views ran on the record), 0 = not, < 0 on an error
-        auto solve_jacobi = [&](CgState& hs) -> int {
-            CgState* cst = (CgState*)(d + o_cg);
-            double* part = (double*)(d + o_part);
-            const uint32_t nbp = (n_views + kRowsPerBlock - 1) / kRowsPerBlock;  // kRowLanes lanes per view
-            double* rbuf[2] = {(double*)(d + o_r), (double*)(d + o_r2)};
-            double* qbuf[2] = {(double*)(d + o_Ap), (double*)(d + o_q2)};
-            double* sbuf[2] = {(double*)(d + o_s), (double*)(d + o_s2)};
-            double* pbuf[2] = {part, part + 6 * ((size_t)nbp + 1)};
-            CgState* record = cst + 2;  // written by the reduce-only launch, read by the host
-            hipLaunchKernelGGL(cg_init_kernel, dim3(nbp), dim3(kCgBlock), 0, st, n_views, (const uint32_t*)(d + o_ptr),
-                               (const uint32_t*)(d + o_aedge), (const int8_t*)(d + o_asign), (const uint8_t*)(d + o_root),
-                               (const double*)(d + o_omega), (const double*)(d + o_w), (double*)(d + o_diag),
-                               (double*)(d + o_x), (double*)(d + o_r), (double*)(d + o_p), qbuf[0], sbuf[0], cst);
-            int cur = 0;           // buffers holding the vectors of the last finished iteration
-            uint32_t launch = 0;   // launches so far: launch j reads parity (j - 1) & 1 of partials / state, writes parity j & 1
-            auto iterate = [&](int mode) {  // 1: init pass, 0: iteration, 2: reduce the last launch's partials into `record`
-                const int prev = (int)((launch + 1) & 1u), next = (int)(launch & 1u);
-                hipLaunchKernelGGL(cg_iteration_kernel, dim3(mode == 2 ? 1u : nbp), dim3(kCgBlock), 0, st, n_views, (const uint32_t*)(d + o_ptr),
-                                   (const uint32_t*)(d + o_aedge), (const uint32_t*)(d + o_aother), (const uint8_t*)(d + o_root),
-                                   (const double*)(d + o_w), (const double*)(d + o_diag), (double*)(d + o_x), (double*)(d + o_p),
-                                   (const double*)rbuf[cur], rbuf[cur ^ 1], (const double*)qbuf[cur], qbuf[cur ^ 1],
-                                   (const double*)sbuf[cur], sbuf[cur ^ 1], mode, launch == 1 ? 1 : 0, cg_tol, (const double*)pbuf[prev],
-                                   pbuf[next], nbp, (const CgState*)(cst + prev), mode == 2 ? record : cst + next);
-                if (mode != 2) {
-                    cur ^= 1;
-                    ++launch;
-                }
-            };
-            iterate(1);
-            return pcg_looks(iterate, finish_views, record, prm.cg_iters, predicted, tree_ok, hs);
-        };
-        bool used_tree_this_iter = false, used_two_this_iter = false, single_now = false;
+        hipLaunchKernelGGL(rot_residual_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, st, d_rot, n_edges, S.R, it < prm.l1_iters ? 1 : 0, sigma,
+                           S.omega, S.w);
+        enum { kTwo, kTree, kSingle, kJacobi } path = kJacobi;  // the solver this step ends up with
+        double cg_it = 0;                                      // its PCG iterations (trace)
         if (use_two) {
-            const int rc = solve_two_level();
+            const int rc = solve_two_level(S, two, predicted2, cg_it);
             if (rc < 0) return rc;
             if (rc == 1) use_two = false;  // a coarse matrix that could not be inverted: this graph stays with the one-level solvers
-            else used_two_this_iter = true;
+            else path = kTwo;
         }
-        if (used_two_this_iter) {
-        } else if (use_tree) {
-            solve_with_tree();
-            used_tree_this_iter = true;
-        } else if (n_views <= single_wg_views) {
+        if (path == kTwo) {
+        } else if (tree.in_use) {
+            path = kTree;
+        } else if (n_views <= knobs.single_wg_views) {
+            path = kSingle;
             uint32_t row_lanes = 16;  // as many lanes per view as keep all views in one pass of the 1024 threads
             while (row_lanes > 1 && (uint64_t)n_views * row_lanes > 1024u) row_lanes >>= 1;
-            hipLaunchKernelGGL(rot_solve_kernel, dim3(1), dim3(1024), 0, st, n_views, (const uint32_t*)(d + o_ptr),
-                               (const uint32_t*)(d + o_aedge), (const uint32_t*)(d + o_aother), (const int8_t*)(d + o_asign),
-                               (const uint8_t*)(d + o_root), (const double*)(d + o_omega), (const double*)(d + o_w),
-                               prm.cg_iters, cg_tol, row_lanes, (double*)(d + o_diag), (double*)(d + o_x), (double*)(d + o_r),
-                               (double*)(d + o_p), (double*)(d + o_Ap), (double*)(d + o_stats));
-            single_now = true;
-            if (tree_ok) {  // a solve that ran into the cap sends this graph to the tree path (see the multi-workgroup branch)
+            hipLaunchKernelGGL(rot_solve_kernel, dim3(1), dim3(1024), 0, st, n_views, S.ptr, S.aedge, S.aother, S.asign, S.root, S.omega, S.w,
+                               prm.cg_iters, S.cg_tol, row_lanes, S.diag, S.x, S.r[0], S.p, S.q[0], S.stats);
+            if (tree.ok) {  // a solve that ran into the cap sends this graph to the tree path (see the multi-workgroup branch)
                 double probe[2] = {0, 0};
-                HIP_TRY(hipMemcpyAsync(probe, d + o_stats, 16, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(probe, S.stats, sizeof probe, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
-                if (probe[1] >= (double)prm.cg_iters) {
-                    use_tree = true;
-                    solve_with_tree();
-                    used_tree_this_iter = true;
-                    single_now = false;
-                }
+                if (probe[1] >= (double)prm.cg_iters) path = kTree;
             }
         } else {  // multi-workgroup PCG: launches are cheap next to a one-CU solve at this size
+            JacobiSolve solve(S);
             CgState hs{};
-            const int done = solve_jacobi(hs);
+            const int done = pcg_looks(solve, st, prm.cg_iters, predicted, tree.ok, hs);
             if (done < 0) return done;
+            cg_it = hs.iters;
             // not converged within the cap: the graph is sparse / sequence-like and Jacobi is the wrong preconditioner for
             // it.  This step is solved again, and all following ones, by the tree-preconditioned kernel, so that the
             // iteration follows the exact-solve trajectory from the start.
-            if (!done && tree_ok) {
-                use_tree = true;
-                solve_with_tree();
-                used_tree_this_iter = true;
+            if (!done && tree.ok) {
+                path = kTree;
             } else if (!done) {  // the truncated solution is the step
-                const int rc = finish_views(nullptr);
+                const int rc = solve.finish(nullptr);
                 if (rc < 0) return rc;
                 HIP_TRY(hipStreamSynchronize(st));
             }
         }
-        double stats[2] = {0, 0};
-        const bool tree_now = used_tree_this_iter;
-        if (single_now) {
-            hipLaunchKernelGGL(rot_update_kernel, dim3((n_views + 255) / 256), dim3(256), 0, st, n_views, (const double*)(d + o_x),
-                               (double*)(d + o_R), (const CgState*)nullptr, (const int*)nullptr);
-            HIP_TRY(hipMemcpyAsync(stats, d + o_stats, 16, hipMemcpyDeviceToHost, st));
+        double stats[2] = {0, 0};  // mean |d|, iterations of the one-workgroup solve
+        if (path == kSingle) {
+            hipLaunchKernelGGL(rot_update_kernel, dim3((n_views + 255) / 256), dim3(256), 0, st, n_views, S.x, (const uint32_t*)nullptr, S.R,
+                               (const CgState*)nullptr, (const int*)nullptr);
+            HIP_TRY(hipMemcpyAsync(stats, S.stats, sizeof stats, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
+            cg_it = stats[1];
         } else {
-            if (tree_now) {
-                const int rc = finish_views(nullptr);
+            if (path == kTree) {
+                tree.in_use = true;
+                solve_with_tree(S, tree);
+                const int rc = queue_step(S, n_views, S.x, nullptr, S.norm, nullptr, nullptr);
                 if (rc < 0) return rc;
                 HIP_TRY(hipStreamSynchronize(st));
             }
             double sum = 0;  // mean |d| = sum / V
-            for (size_t b2 = 0; b2 < norm_host.size(); b2 += 3) sum += norm_host[b2];
+            for (size_t b2 = 0; b2 < S.norm_host.size(); b2 += 3) sum += S.norm_host[b2];
             stats[0] = sum / (double)n_views;
         }
         iters = it + 1;
-        if (trace) {  // PGI_ROTAVG_TRACE=1: one line per outer iteration
-            double cg_it = stats[1];
-            if (used_two_this_iter) {
-                cg_it = two_iters;
-            } else if (tree_now) {
+        if (knobs.trace) {
+            if (path == kTree) {
                 double its[3];
-                HIP_TRY(hipMemcpyAsync(its, d + o_its, 24, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(its, S.its, sizeof its, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
                 cg_it = -std::max(its[0], std::max(its[1], its[2]));  // printed negative: tree-preconditioned iterations
-            } else if (n_views > single_wg_views) {
-                CgState hs;
-                HIP_TRY(hipMemcpyAsync(&hs, d + o_cg + 2 * sizeof(CgState), sizeof hs, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                cg_it = hs.iters;
             }
             std::fprintf(stderr, "[rotavg] outer %2u (%s): %3.0f PCG iterations%s, mean step %.3e rad\n", it, it < prm.l1_iters ? "L1" : "IRLS", cg_it,
-                         used_two_this_iter ? " (two-level)" : "", stats[0]);
+                         path == kTwo ? " (two-level)" : "", stats[0]);
         }
         if (stats[0] < prm.tol) break;
     }
     clk.mark("solve: outer iterations");
-    HIP_TRY(hipMemcpyAsync(h_R_out, d + o_R, V * 72, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_R_out, S.R, (size_t)n_views * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     clk.mark("solve: rotations back");
     if (h_iters_out) *h_iters_out = iters;
@@ -1967,7 +1455,8 @@ int pgi_rotation_average(pgi_ctx* ctx, const pgi_rot_edge* h_edges, uint32_t n_e
     if (n_views == 0) return PGI_SUCCESS;
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));
-    PhaseClock clk;
+    const RotavgKnobs knobs = read_rotavg_knobs();
+    PhaseClock clk(knobs.timing);
     std::vector<uint32_t> src(n_edges), dst(n_edges), tree;
     std::vector<double> wt(n_edges);
     for (uint32_t e = 0; e < n_edges; ++e) {
@@ -1989,15 +1478,13 @@ int pgi_rotation_average(pgi_ctx* ctx, const pgi_rot_edge* h_edges, uint32_t n_e
     }
     static_assert(sizeof(RotEdgeDev) == sizeof(pgi_rot_edge), "edge layout");
     RotEdgeDev* d_rot = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_rot, (size_t)n_edges * sizeof(RotEdgeDev)));
-    struct Guard {
-        void* p;
-        ~Guard() { (void)hipFree(p); }
-    } guard{d_rot};
+    DeviceWorkspace ws;
+    ws.add(d_rot, n_edges);
+    HIP_TRY(ws.alloc());
     HIP_TRY(hipMemcpyAsync(d_rot, h_edges, (size_t)n_edges * sizeof(pgi_rot_edge), hipMemcpyHostToDevice, ctx->stream));
     if (clk.on) (void)hipStreamSynchronize(ctx->stream);
     clk.mark("host edges: edge table to the device");
-    return rotavg_solve(ctx, prm, n_views, n_edges, src.data(), dst.data(), d_rot, R, is_root, adj, h_R_out, h_iters_out);
+    return rotavg_solve(ctx, knobs, prm, n_views, n_edges, src.data(), dst.data(), d_rot, R, is_root, adj, h_R_out, h_iters_out);
 }
 
 int pgi_rotation_average_edges(pgi_ctx* ctx, const pgi_edge* d_edges, const uint32_t* h_src, const uint32_t* h_dst,
@@ -2012,7 +1499,8 @@ int pgi_rotation_average_edges(pgi_ctx* ctx, const pgi_edge* d_edges, const uint
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    PhaseClock clk;
+    const RotavgKnobs knobs = read_rotavg_knobs();
+    PhaseClock clk(knobs.timing);
     // (status, n_inl) of every record: an 8-byte column of the 200-byte table
     struct Meta { int32_t status; uint32_t n_inl; };
     std::vector<Meta> meta(n_pairs);
@@ -2047,35 +1535,28 @@ int pgi_rotation_average_edges(pgi_ctx* ctx, const pgi_edge* d_edges, const uint
         return PGI_SUCCESS;
     }
     const size_t nT = tree.size();
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_rot = 0, o_idx = up((size_t)nE * sizeof(RotEdgeDev)), o_src = o_idx + up((size_t)nE * 4),
-                 o_dst = o_src + up((size_t)nE * 4), o_wt = o_dst + up((size_t)nE * 4), o_tree = o_wt + up((size_t)nE * 8),
-                 o_treeR = o_tree + up(nT * 4), total = o_treeR + up(nT * 72);
-    char* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, total));
-    struct Guard {
-        void* p;
-        ~Guard() { (void)hipFree(p); }
-    } guard{d};
-    HIP_TRY(hipMemcpyAsync(d + o_idx, idx.data(), (size_t)nE * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_src, src.data(), (size_t)nE * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_dst, dst.data(), (size_t)nE * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_wt, wt.data(), (size_t)nE * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_tree, tree.data(), nT * 4, hipMemcpyHostToDevice, st));
-    RotEdgeDev* d_rot = (RotEdgeDev*)(d + o_rot);
-    hipLaunchKernelGGL(rot_edges_from_table_kernel, dim3((nE + 255) / 256), dim3(256), 0, st, d_edges, (const uint32_t*)(d + o_idx),
-                       (const uint32_t*)(d + o_src), (const uint32_t*)(d + o_dst), (const double*)(d + o_wt), nE, d_rot);
-    hipLaunchKernelGGL(rot_gather_R_kernel, dim3(((uint32_t)nT + 255) / 256), dim3(256), 0, st, d_rot, (const uint32_t*)(d + o_tree),
-                       (uint32_t)nT, (double*)(d + o_treeR));
+    RotEdgeDev* d_rot;
+    uint32_t *d_idx, *d_src, *d_dst, *d_tree;
+    double *d_wt, *d_treeR;
+    DeviceWorkspace ws;
+    ws.add(d_rot, nE); ws.add(d_idx, nE); ws.add(d_src, nE); ws.add(d_dst, nE); ws.add(d_wt, nE); ws.add(d_tree, nT); ws.add(d_treeR, 9 * nT);
+    HIP_TRY(ws.alloc());
+    HIP_TRY(upload(d_idx, idx, st));
+    HIP_TRY(upload(d_src, src, st));
+    HIP_TRY(upload(d_dst, dst, st));
+    HIP_TRY(upload(d_wt, wt, st));
+    HIP_TRY(upload(d_tree, tree, st));
+    hipLaunchKernelGGL(rot_edges_from_table_kernel, dim3((nE + 255) / 256), dim3(256), 0, st, d_edges, d_idx, d_src, d_dst, d_wt, nE, d_rot);
+    hipLaunchKernelGGL(rot_gather_R_kernel, dim3(((uint32_t)nT + 255) / 256), dim3(256), 0, st, d_rot, d_tree, (uint32_t)nT, d_treeR);
     std::vector<double> treeR(nT * 9);
-    HIP_TRY(hipMemcpyAsync(treeR.data(), d + o_treeR, nT * 72, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(treeR.data(), d_treeR, treeR.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::vector<uint32_t> slot(nE, 0u);  // edge -> position in the forest list
     for (size_t k = 0; k < nT; ++k) slot[tree[k]] = (uint32_t)k;
     clk.mark("edges: device edge table, forest rotations back");
     forest_bfs_init(n_views, adj, [&](uint32_t e) { return &treeR[9 * (size_t)slot[e]]; }, R, is_root);
     clk.mark("edges: forest initialisation (host)");
-    return rotavg_solve(ctx, prm, n_views, nE, src.data(), dst.data(), d_rot, R, is_root, adj, h_R_out, h_iters_out);
+    return rotavg_solve(ctx, knobs, prm, n_views, nE, src.data(), dst.data(), d_rot, R, is_root, adj, h_R_out, h_iters_out);
 }
 
 }  // extern "C"

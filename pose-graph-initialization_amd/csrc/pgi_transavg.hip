@@ -21,6 +21,8 @@
 // inner error vanishes with it.  Unlike the rotation solve the three coordinates are coupled through the 3 x 3 blocks.
 // Multi-GPU: replicated on every rank after the all-gather of the edge records, like the rotation solve.
 #include "pgi_internal.hpp"
+#include "pgi_graph_host.hpp"
+#include "pgi_reduce.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -172,19 +174,6 @@ TDEV void view_product(uint32_t v, const uint32_t* __restrict__ adj_ptr, const u
     }
 }
 
-// sum over the 256 threads in a fixed tree order, returned to all of them
-__device__ double block_sum_256(double v, double* red /* 256 */, int tid) {
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // ---- small graphs: the whole solve in one workgroup, thread v owns view v (its vectors stay in registers; the search
 // direction is shared through LDS).  stats: [1] = PCG iterations.
 __global__ __launch_bounds__(256) void trn_solve_kernel(uint32_t n_views, const uint32_t* __restrict__ adj_ptr,
@@ -207,7 +196,7 @@ __global__ __launch_bounds__(256) void trn_solve_kernel(uint32_t n_views, const 
     sym_mul(Dinv, r, z);
 #pragma unroll
     for (int k = 0; k < 3; ++k) p[k] = z[k];
-    double rz = block_sum_256(r[0] * z[0] + r[1] * z[1] + r[2] * z[2], red, tid);
+    double rz = block_tree_sum<256>(r[0] * z[0] + r[1] * z[1] + r[2] * z[2], red, tid);
     const double rz0 = rz;
     uint32_t it = 0;
     for (; it < cg_iters; ++it) {
@@ -219,7 +208,7 @@ __global__ __launch_bounds__(256) void trn_solve_kernel(uint32_t n_views, const 
         if (live)
             view_product(v, adj_ptr, adj_edge, adj_other, P, p,
                          [&](uint32_t o, double* po) { po[0] = pl[3 * o]; po[1] = pl[3 * o + 1]; po[2] = pl[3 * o + 2]; }, q);
-        const double pAp = block_sum_256(p[0] * q[0] + p[1] * q[1] + p[2] * q[2], red, tid);  // (its barriers also retire pl)
+        const double pAp = block_tree_sum<256>(p[0] * q[0] + p[1] * q[1] + p[2] * q[2], red, tid);  // (its barriers also retire pl)
         const double alpha = pAp > 0.0 ? rz / pAp : 0.0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -227,7 +216,7 @@ __global__ __launch_bounds__(256) void trn_solve_kernel(uint32_t n_views, const 
             r[k] -= alpha * q[k];
         }
         sym_mul(Dinv, r, z);
-        const double rzn = block_sum_256(r[0] * z[0] + r[1] * z[1] + r[2] * z[2], red, tid);
+        const double rzn = block_tree_sum<256>(r[0] * z[0] + r[1] * z[1] + r[2] * z[2], red, tid);
         const double beta = rz > 0.0 ? rzn / rz : 0.0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) p[k] = z[k] + beta * p[k];
@@ -251,17 +240,6 @@ struct TrnCgState {
     double rz, rz0, iters;
     int done, pad;
 };
-TDEV double wave_sum_64(double v) {  // xor tree: the same order on every call, the sum in every lane
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-TDEV double reduce_partials(const double* __restrict__ part, uint32_t n_blocks, int tid) {
-    double s = 0.0;
-    for (uint32_t b = (uint32_t)tid; b < n_blocks; b += kTrnBlock) s += part[b];
-    return wave_sum_64(s);
-}
-
 __global__ __launch_bounds__(kTrnBlock) void trn_cg_init_kernel(uint32_t n_views, const uint32_t* __restrict__ adj_ptr,
                                                                 const uint32_t* __restrict__ adj_edge, const uint32_t* __restrict__ adj_other,
                                                                 const int8_t* __restrict__ adj_sign, const uint8_t* __restrict__ is_root,
@@ -291,7 +269,7 @@ __global__ __launch_bounds__(kTrnBlock) void trn_cg_init_kernel(uint32_t n_views
             p0[i] = 0.0;
         }
     }
-    const double s = wave_sum_64(r[0] * z[0] + r[1] * z[1] + r[2] * z[2]);
+    const double s = wave_sum(r[0] * z[0] + r[1] * z[1] + r[2] * z[2]);
     if (tid == 0) part_rz[blockIdx.x] = s;
     if (blockIdx.x == 0 && tid == 0) *st = TrnCgState{0.0, 0.0, 0.0, 0, 0};
 }
@@ -310,7 +288,7 @@ __global__ __launch_bounds__(kTrnBlock) void trn_cg_direction_kernel(uint32_t n_
         if (blockIdx.x == 0 && tid == 0) *st_next = sp;
         return;
     }
-    const double rz = reduce_partials(part_rz, n_blocks, tid);
+    const double rz = wave_sum(strided_sum<kTrnBlock>(part_rz, n_blocks, 1, tid));
     const double rz0 = first ? rz : sp.rz0;
     const double beta = (!first && sp.rz > 0.0) ? rz / sp.rz : 0.0;
     const bool done = !(rz > tol * tol * rz0);
@@ -334,7 +312,7 @@ __global__ __launch_bounds__(kTrnBlock) void trn_cg_direction_kernel(uint32_t n_
             q[3 * (size_t)v + k] = y[k];
         }
     }
-    const double s = wave_sum_64(pv[0] * y[0] + pv[1] * y[1] + pv[2] * y[2]);
+    const double s = wave_sum(pv[0] * y[0] + pv[1] * y[1] + pv[2] * y[2]);
     if (tid == 0) part_pq[blockIdx.x] = s;
 }
 
@@ -346,7 +324,7 @@ __global__ __launch_bounds__(kTrnBlock) void trn_cg_update_kernel(uint32_t n_vie
     const int tid = threadIdx.x;
     const TrnCgState s = *st;
     if (s.done) return;  // (uniform)
-    const double pq = reduce_partials(part_pq, n_blocks, tid);
+    const double pq = wave_sum(strided_sum<kTrnBlock>(part_pq, n_blocks, 1, tid));
     const double alpha = pq > 0.0 ? s.rz / pq : 0.0;
     const uint32_t v = blockIdx.x * kTrnBlock + (uint32_t)tid;
     double rn[3] = {0, 0, 0}, zn[3] = {0, 0, 0};
@@ -367,7 +345,7 @@ __global__ __launch_bounds__(kTrnBlock) void trn_cg_update_kernel(uint32_t n_vie
             z[3 * (size_t)v + k] = zn[k];
         }
     }
-    const double t = wave_sum_64(rn[0] * zn[0] + rn[1] * zn[1] + rn[2] * zn[2]);
+    const double t = wave_sum(rn[0] * zn[0] + rn[1] * zn[1] + rn[2] * zn[2]);
     if (tid == 0) part_rz[blockIdx.x] = t;
 }
 
@@ -384,44 +362,16 @@ __global__ __launch_bounds__(256) void trn_step_kernel(uint32_t n_views, const d
         c[3 * (size_t)v + 1] += b;
         c[3 * (size_t)v + 2] += d;
     }
-    s = block_sum_256(s, red, tid);
+    s = block_tree_sum<256>(s, red, tid);
     if (tid == 0) stats[0] = s / (double)n_views;
 }
 
-// ---- host: maximum-weight spanning forest + BFS initialisation (the forest and the roots of the rotation averaging:
-// Kruskal over (weight desc, edge index asc), roots = the smallest view of every component) --------------------------------
-struct TrnForestEdge {
-    uint32_t edge, other;  // other | backwards << 31
-};
-void trn_spanning_forest(uint32_t V, const uint32_t* src, const uint32_t* dst, const double* weight, uint32_t nE,
-                         std::vector<uint32_t>& tree, std::vector<std::vector<TrnForestEdge>>& adj) {
-    std::vector<uint32_t> order(nE);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return weight[a] > weight[b]; });
-    std::vector<uint32_t> parent(V);
-    std::iota(parent.begin(), parent.end(), 0u);
-    auto find = [&](uint32_t a) {
-        while (parent[a] != a) {
-            parent[a] = parent[parent[a]];
-            a = parent[a];
-        }
-        return a;
-    };
-    adj.assign(V, {});
-    tree.clear();
-    for (uint32_t e : order) {
-        const uint32_t a = find(src[e]), b = find(dst[e]);
-        if (a == b) continue;
-        parent[std::max(a, b)] = std::min(a, b);
-        adj[src[e]].push_back({e, dst[e]});
-        adj[dst[e]].push_back({e, src[e] | 0x80000000u});
-        tree.push_back(e);
-        if (tree.size() + 1 == V) break;
-    }
-}
+// ---- host: BFS initialisation over the maximum-weight spanning forest (spanning_forest of pgi_graph_host.hpp: the forest and
+// the roots of the rotation averaging -- Kruskal over (weight desc, edge index asc), roots = the smallest view of every
+// component.  The weights that reach it here are finite and not negative: the entry points see to that.) ----------------------
 // c_root = 0; along a tree edge c_dst = c_src - gamma, walked backwards c_src = c_dst + gamma.  dir_of(e): 3 doubles.
 template <class DirOf>
-void trn_forest_init(uint32_t V, const std::vector<std::vector<TrnForestEdge>>& adj, DirOf dir_of, std::vector<double>& c,
+void trn_forest_init(uint32_t V, const std::vector<std::vector<ForestEdge>>& adj, DirOf dir_of, std::vector<double>& c,
                      std::vector<uint8_t>& is_root) {
     c.assign((size_t)V * 3, 0.0);
     is_root.assign(V, 0);
@@ -434,7 +384,7 @@ void trn_forest_init(uint32_t V, const std::vector<std::vector<TrnForestEdge>>& 
         queue.assign(1, root);
         for (size_t h = 0; h < queue.size(); ++h) {
             const uint32_t u = queue[h];
-            for (const TrnForestEdge& pr : adj[u]) {
+            for (const ForestEdge& pr : adj[u]) {
                 const uint32_t v = pr.other & 0x7FFFFFFFu;
                 if (seen[v]) continue;
                 seen[v] = 1;
@@ -451,61 +401,28 @@ void trn_forest_init(uint32_t V, const std::vector<std::vector<TrnForestEdge>>& 
 int transavg_solve(pgi_ctx* ctx, const pgi_transavg_params& prm, uint32_t n_views, uint32_t n_edges, const uint32_t* h_src,
                    const uint32_t* h_dst, const TrnEdgeDev* d_trn, const std::vector<double>& c0, const std::vector<uint8_t>& is_root,
                    double* h_c_out, uint32_t* h_iters_out) {
-    // CSR adjacency, incidences in edge order; sign +1: the view is the edge's src
-    std::vector<uint32_t> ptr(n_views + 1, 0), aedge(2 * (size_t)n_edges), aother(2 * (size_t)n_edges);
-    std::vector<int8_t> asign(2 * (size_t)n_edges);
-    for (uint32_t e = 0; e < n_edges; ++e) {
-        ++ptr[h_src[e] + 1];
-        ++ptr[h_dst[e] + 1];
-    }
-    for (uint32_t k = 0; k < n_views; ++k) ptr[k + 1] += ptr[k];
-    {
-        std::vector<uint32_t> fill(ptr.begin(), ptr.end() - 1);
-        for (uint32_t e = 0; e < n_edges; ++e) {
-            uint32_t a = fill[h_src[e]]++;
-            aedge[a] = e; aother[a] = h_dst[e]; asign[a] = +1;
-            a = fill[h_dst[e]]++;
-            aedge[a] = e; aother[a] = h_src[e]; asign[a] = -1;
-        }
-    }
+    const IncidenceCsr adj = build_incidence_csr(n_views, n_edges, h_src, h_dst, +1);  // sign +1: the view is the edge's src
     const size_t V = n_views, E = n_edges;
     const uint32_t n_blocks = (n_views + kTrnBlock - 1) / kTrnBlock;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_c = carve(V * 24), o_ptr = carve((V + 1) * 4), o_aedge = carve(2 * E * 4), o_aother = carve(2 * E * 4),
-                 o_asign = carve(2 * E), o_root = carve(V), o_P = carve(E * 48), o_g = carve(E * 24), o_Dinv = carve(V * 48),
-                 o_x = carve(V * 24), o_r = carve(V * 24), o_z = carve(V * 24), o_p0 = carve(V * 24), o_p1 = carve(V * 24),
-                 o_q = carve(V * 24), o_prz = carve((size_t)n_blocks * 8), o_ppq = carve((size_t)n_blocks * 8),
-                 o_st = carve(2 * sizeof(TrnCgState)), o_stats = carve(16), o_cnt = carve(4);
-    char* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, off));
-    struct Guard {
-        char* p;
-        ~Guard() { (void)hipFree(p); }
-    } guard{d};
+    double *d_c, *d_P, *d_g, *d_Dinv, *d_x, *d_r, *d_z, *d_pbuf[2], *d_q, *d_prz, *d_ppq, *d_stats;
+    uint32_t *d_ptr, *d_aedge, *d_aother;
+    int8_t* d_asign;
+    uint8_t* d_root;
+    TrnCgState* d_st;
+    unsigned int* d_cnt;
+    DeviceWorkspace ws;
+    ws.add(d_c, 3 * V); ws.add(d_ptr, V + 1); ws.add(d_aedge, 2 * E); ws.add(d_aother, 2 * E); ws.add(d_asign, 2 * E); ws.add(d_root, V);
+    ws.add(d_P, 6 * E); ws.add(d_g, 3 * E); ws.add(d_Dinv, 6 * V); ws.add(d_x, 3 * V); ws.add(d_r, 3 * V); ws.add(d_z, 3 * V);
+    ws.add(d_pbuf[0], 3 * V); ws.add(d_pbuf[1], 3 * V); ws.add(d_q, 3 * V); ws.add(d_prz, n_blocks); ws.add(d_ppq, n_blocks);
+    ws.add(d_st, 2); ws.add(d_stats, 2); ws.add(d_cnt, 1);
+    HIP_TRY(ws.alloc());
     hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_c, c0.data(), V * 24, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_ptr, ptr.data(), (V + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_aedge, aedge.data(), 2 * E * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_aother, aother.data(), 2 * E * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_asign, asign.data(), 2 * E, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_root, is_root.data(), V, hipMemcpyHostToDevice, st));
-    const uint32_t* d_ptr = (const uint32_t*)(d + o_ptr);
-    const uint32_t* d_aedge = (const uint32_t*)(d + o_aedge);
-    const uint32_t* d_aother = (const uint32_t*)(d + o_aother);
-    const int8_t* d_asign = (const int8_t*)(d + o_asign);
-    const uint8_t* d_root = (const uint8_t*)(d + o_root);
-    double* d_c = (double*)(d + o_c);
-    double* d_P = (double*)(d + o_P);
-    double* d_g = (double*)(d + o_g);
-    double* d_x = (double*)(d + o_x);
-    double* d_pbuf[2] = {(double*)(d + o_p0), (double*)(d + o_p1)};
-    TrnCgState* d_st = (TrnCgState*)(d + o_st);
-    unsigned int* d_cnt = (unsigned int*)(d + o_cnt);
+    HIP_TRY(upload(d_c, c0, st));
+    HIP_TRY(upload(d_ptr, adj.ptr, st));
+    HIP_TRY(upload(d_aedge, adj.edge, st));
+    HIP_TRY(upload(d_aother, adj.other, st));
+    HIP_TRY(upload(d_asign, adj.sign, st));
+    HIP_TRY(upload(d_root, is_root, st));
 
     const bool trace = std::getenv("PGI_TRANSAVG_TRACE") != nullptr;
     double cg_tol = kTrnInnerTolerance;
@@ -518,16 +435,15 @@ int transavg_solve(pgi_ctx* ctx, const pgi_transavg_params& prm, uint32_t n_view
     uint32_t iters = 0, predicted = 0;
     for (uint32_t it = 0; it < prm.iters; ++it) {
         HIP_TRY(hipMemsetAsync(d_cnt, 0, 4, st));
-        hipLaunchKernelGGL(trn_model_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, st, d_trn, n_edges, (const double*)d_c, prm.eps,
-                           prm.delta, d_P, d_g, d_cnt);
+        hipLaunchKernelGGL(trn_model_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, st, d_trn, n_edges, d_c, prm.eps, prm.delta, d_P,
+                           d_g, d_cnt);
         double cg_done = 0.0;
         if (single) {
-            hipLaunchKernelGGL(trn_solve_kernel, dim3(1), dim3(256), 0, st, n_views, d_ptr, d_aedge, d_aother, d_asign, d_root,
-                               (const double*)d_P, (const double*)d_g, (const double*)d_c, cap, cg_tol, d_x, (double*)(d + o_stats));
+            hipLaunchKernelGGL(trn_solve_kernel, dim3(1), dim3(256), 0, st, n_views, d_ptr, d_aedge, d_aother, d_asign, d_root, d_P,
+                               d_g, d_c, cap, cg_tol, d_x, d_stats);
         } else {
             hipLaunchKernelGGL(trn_cg_init_kernel, dim3(n_blocks), dim3(kTrnBlock), 0, st, n_views, d_ptr, d_aedge, d_aother, d_asign,
-                               d_root, (const double*)d_P, (const double*)d_g, (const double*)d_c, (double*)(d + o_Dinv), d_x,
-                               (double*)(d + o_r), (double*)(d + o_z), d_pbuf[0], (double*)(d + o_prz), d_st);
+                               d_root, d_P, d_g, d_c, d_Dinv, d_x, d_r, d_z, d_pbuf[0], d_prz, d_st);
             // The host looks at the state record between chunks of iterations (each look a round trip): first after what
             // the previous outer step's solve needed plus two (consecutive systems differ by their weights only), then every 16.
             uint32_t ci = 0;
@@ -537,13 +453,10 @@ int transavg_solve(pgi_ctx* ctx, const pgi_transavg_params& prm, uint32_t n_view
                 const uint32_t target = std::min<uint32_t>(cap, ci + (ci == 0 ? std::max<uint32_t>(16u, predicted + 2u) : 16u));
                 for (; ci < target; ++ci) {
                     hipLaunchKernelGGL(trn_cg_direction_kernel, dim3(n_blocks), dim3(kTrnBlock), 0, st, n_views, d_ptr, d_aedge, d_aother,
-                                       d_root, (const double*)d_P, (const double*)(d + o_z), (const double*)d_pbuf[par], d_pbuf[par ^ 1],
-                                       (double*)(d + o_q), (const double*)(d + o_prz), (double*)(d + o_ppq), n_blocks, ci == 0 ? 1 : 0,
-                                       cg_tol, (const TrnCgState*)(d_st + par), d_st + (par ^ 1));
-                    hipLaunchKernelGGL(trn_cg_update_kernel, dim3(n_blocks), dim3(kTrnBlock), 0, st, n_views, (const double*)(d + o_Dinv),
-                                       (const double*)d_pbuf[par ^ 1], (const double*)(d + o_q), d_x, (double*)(d + o_r),
-                                       (double*)(d + o_z), (const double*)(d + o_ppq), (double*)(d + o_prz), n_blocks,
-                                       (const TrnCgState*)(d_st + (par ^ 1)));
+                                       d_root, d_P, d_z, d_pbuf[par], d_pbuf[par ^ 1], d_q, d_prz, d_ppq, n_blocks, ci == 0 ? 1 : 0, cg_tol,
+                                       d_st + par, d_st + (par ^ 1));
+                    hipLaunchKernelGGL(trn_cg_update_kernel, dim3(n_blocks), dim3(kTrnBlock), 0, st, n_views, d_Dinv, d_pbuf[par ^ 1], d_q, d_x,
+                                       d_r, d_z, d_ppq, d_prz, n_blocks, d_st + (par ^ 1));
                     par ^= 1;
                 }
                 HIP_TRY(hipMemcpyAsync(&hs, d_st + par, sizeof hs, hipMemcpyDeviceToHost, st));
@@ -553,10 +466,10 @@ int transavg_solve(pgi_ctx* ctx, const pgi_transavg_params& prm, uint32_t n_view
             cg_done = hs.iters;
             predicted = (uint32_t)hs.iters;
         }
-        hipLaunchKernelGGL(trn_step_kernel, dim3(1), dim3(256), 0, st, n_views, (const double*)d_x, d_c, (double*)(d + o_stats));
+        hipLaunchKernelGGL(trn_step_kernel, dim3(1), dim3(256), 0, st, n_views, d_x, d_c, d_stats);
         double stats[2] = {0, 0};
         unsigned int n_clamped = 0;
-        HIP_TRY(hipMemcpyAsync(stats, d + o_stats, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(stats, d_stats, sizeof stats, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&n_clamped, d_cnt, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipGetLastError());
@@ -566,7 +479,7 @@ int transavg_solve(pgi_ctx* ctx, const pgi_transavg_params& prm, uint32_t n_view
                          single ? stats[1] : cg_done, n_clamped, n_edges, stats[0]);
         if (stats[0] < prm.tol) break;
     }
-    HIP_TRY(hipMemcpyAsync(h_c_out, d_c, V * 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_c_out, d_c, 3 * V * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h_iters_out) *h_iters_out = iters;
     return PGI_SUCCESS;
@@ -619,8 +532,8 @@ int pgi_translation_average(pgi_ctx* ctx, const pgi_trans_edge* h_edges, uint32_
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));
     std::vector<uint32_t> tree;
-    std::vector<std::vector<TrnForestEdge>> adj;
-    trn_spanning_forest(n_views, src.data(), dst.data(), wt.data(), n_edges, tree, adj);
+    std::vector<std::vector<ForestEdge>> adj;
+    spanning_forest(n_views, src.data(), dst.data(), wt.data(), n_edges, tree, adj);
     std::vector<double> c0;
     std::vector<uint8_t> is_root;
     trn_forest_init(n_views, adj, [&](uint32_t e) { return (const double*)edges[e].dir; }, c0, is_root);
@@ -629,12 +542,10 @@ int pgi_translation_average(pgi_ctx* ctx, const pgi_trans_edge* h_edges, uint32_
         return PGI_SUCCESS;
     }
     TrnEdgeDev* d_trn = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_trn, (size_t)n_edges * sizeof(TrnEdgeDev)));
-    struct Guard {
-        void* p;
-        ~Guard() { (void)hipFree(p); }
-    } guard{d_trn};
-    HIP_TRY(hipMemcpyAsync(d_trn, edges.data(), (size_t)n_edges * sizeof(TrnEdgeDev), hipMemcpyHostToDevice, ctx->stream));
+    DeviceWorkspace ws;
+    ws.add(d_trn, n_edges);
+    HIP_TRY(ws.alloc());
+    HIP_TRY(upload(d_trn, edges, ctx->stream));
     return transavg_solve(ctx, prm, n_views, n_edges, src.data(), dst.data(), d_trn, c0, is_root, h_c_out, h_iters_out);
 }
 
@@ -675,42 +586,36 @@ int pgi_translation_average_edges(pgi_ctx* ctx, const pgi_edge* d_edges, const u
     const uint32_t nE = (uint32_t)idx.size();
     if (h_edges_used) *h_edges_used = nE;
     std::vector<uint32_t> tree;
-    std::vector<std::vector<TrnForestEdge>> adj;
-    trn_spanning_forest(n_views, src.data(), dst.data(), wt.data(), nE, tree, adj);
+    std::vector<std::vector<ForestEdge>> adj;
+    spanning_forest(n_views, src.data(), dst.data(), wt.data(), nE, tree, adj);
     std::vector<double> c0;
     std::vector<uint8_t> is_root;
     if (nE == 0) {
-        memset(h_c_out, 0, (size_t)n_views * 24);
+        memset(h_c_out, 0, (size_t)n_views * 3 * sizeof(double));
         return PGI_SUCCESS;
     }
     const size_t nT = tree.size(), V = n_views;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_trn = 0, o_idx = up((size_t)nE * sizeof(TrnEdgeDev)), o_src = o_idx + up((size_t)nE * 4),
-                 o_dst = o_src + up((size_t)nE * 4), o_wt = o_dst + up((size_t)nE * 8), o_R = o_wt + up((size_t)nE * 8),
-                 o_tree = o_R + up(V * 72), o_treeD = o_tree + up(nT * 4), o_bad = o_treeD + up(nT * 24), total = o_bad + 256;
-    char* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, total));
-    struct Guard {
-        void* p;
-        ~Guard() { (void)hipFree(p); }
-    } guard{d};
-    HIP_TRY(hipMemcpyAsync(d + o_idx, idx.data(), (size_t)nE * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_src, src.data(), (size_t)nE * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_dst, dst.data(), (size_t)nE * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_wt, wt.data(), (size_t)nE * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_R, h_R_global, V * 72, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_tree, tree.data(), nT * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d + o_bad, 0, 4, st));
-    TrnEdgeDev* d_trn = (TrnEdgeDev*)(d + o_trn);
-    hipLaunchKernelGGL(trn_directions_kernel, dim3((nE + 255) / 256), dim3(256), 0, st, d_edges, (const uint32_t*)(d + o_idx),
-                       (const uint32_t*)(d + o_src), (const uint32_t*)(d + o_dst), (const double*)(d + o_wt), (const double*)(d + o_R), nE,
-                       d_trn, (int*)(d + o_bad));
-    hipLaunchKernelGGL(trn_gather_dir_kernel, dim3(((uint32_t)nT + 255) / 256), dim3(256), 0, st, (const TrnEdgeDev*)d_trn,
-                       (const uint32_t*)(d + o_tree), (uint32_t)nT, (double*)(d + o_treeD));
+    TrnEdgeDev* d_trn;
+    uint32_t *d_idx, *d_src, *d_dst, *d_tree;
+    double *d_wt, *d_R, *d_treeD;
+    int* d_bad;
+    DeviceWorkspace ws;
+    ws.add(d_trn, nE); ws.add(d_idx, nE); ws.add(d_src, nE); ws.add(d_dst, nE); ws.add(d_wt, nE); ws.add(d_R, 9 * V); ws.add(d_tree, nT);
+    ws.add(d_treeD, 3 * nT); ws.add(d_bad, 1);
+    HIP_TRY(ws.alloc());
+    HIP_TRY(upload(d_idx, idx, st));
+    HIP_TRY(upload(d_src, src, st));
+    HIP_TRY(upload(d_dst, dst, st));
+    HIP_TRY(upload(d_wt, wt, st));
+    HIP_TRY(hipMemcpyAsync(d_R, h_R_global, 9 * V * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(upload(d_tree, tree, st));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), st));
+    hipLaunchKernelGGL(trn_directions_kernel, dim3((nE + 255) / 256), dim3(256), 0, st, d_edges, d_idx, d_src, d_dst, d_wt, d_R, nE, d_trn, d_bad);
+    hipLaunchKernelGGL(trn_gather_dir_kernel, dim3(((uint32_t)nT + 255) / 256), dim3(256), 0, st, d_trn, d_tree, (uint32_t)nT, d_treeD);
     std::vector<double> treeD(nT * 3);
     int bad = 0;
-    HIP_TRY(hipMemcpyAsync(treeD.data(), d + o_treeD, nT * 24, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&bad, d + o_bad, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(treeD.data(), d_treeD, treeD.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (bad) return fail(PGI_ERR_INVALID, "edge direction zero or not finite");
     std::vector<uint32_t> slot(nE, 0u);  // edge -> position in the forest list

@@ -651,7 +651,7 @@ def _mirror_tree_plan(F):
 def mirror_solve(g, F, om, w, n, path, tol, perm=None, cg_form=False, agg=None):
     """One inner solve in float64 as the kernels write it: per-view sums over the incidences in edge order (or in the order
     `perm` ranks the edges), the plain recurrences (rot_solve_kernel, rot_solve_tree_kernel) or the Chronopoulos-Gear form
-    with the neighbours' z rebuilt from the previous vectors (cg_iteration_kernel, cg2_iteration_kernel); the tree solve by
+    with the neighbours' z rebuilt from the previous vectors (cg_iteration_kernel, one- and two-level); the tree solve by
     the two prefix sums; Ac^-1 by Gauss-Jordan without pivoting, symmetrised.  -> (x [V,3], iterations run per axis)."""
     V, src, dst = g["V"], g["src"], g["dst"]
     E = len(src)
@@ -845,7 +845,7 @@ def tree_graphs():
 
 
 def two_level_graphs():
-    """cg2_* (PGI_ROTAVG_TWO_LEVEL = 2)."""
+    """cg_*_kernel<true>, cg2_coarse_* (PGI_ROTAVG_TWO_LEVEL = 2)."""
     return {"V20": dense_multigraph(20, seed=20), "V100": random_graph(100, 10, seed=100), "band700": seq_graph(700, 12, seed=17),
             "merge": seq_graph(105, 4, seed=18), "components": random_graph(200, 10, seed=19, components=2)}
 

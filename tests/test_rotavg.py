@@ -99,6 +99,27 @@ def test_hip_rotation_averaging_matches_oracle(V, k, noise, outl, comps):
 
 
 @pytest.mark.gpu
+def test_many_workgroup_jacobi_with_more_than_256_row_blocks(monkeypatch):
+    """V = 16 * 256 + 17 = 4113 is the smallest graph with more than 256 row blocks (16 views per block): every launch's
+    strided sum over the previous launch's block partials takes a second pass there, which no smaller graph reaches.  The
+    many-workgroup Jacobi path is forced; ~6 random neighbours per view, one component; the oracle's tolerance."""
+    from pyposegraphbuilder import Engine
+    monkeypatch.setenv("PGI_ROTAVG_SINGLE_WG_VIEWS", "0")
+    monkeypatch.setenv("PGI_ROTAVG_TWO_LEVEL", "0")
+    V = 16 * 256 + 17
+    eng = Engine()
+    src, dst, Rrel, w, Rgt, _ = RO.make_graph(V, 6, 1.0, 0.15, seed=11)
+    R, iters = eng.rotation_average(src, dst, Rrel, w, V)
+    Ro, iters_o = RO.rotation_average(V, src, dst, Rrel, w)
+    d = np.einsum("kij,kmj->kim", R, Ro)
+    ang = np.arccos(np.clip((np.trace(d, axis1=1, axis2=2) - 1) / 2, -1, 1))
+    print("V %d, %d edges: %d outer iterations (oracle %d), max diff %.2e rad" % (V, len(src), iters, iters_o, ang.max()))
+    assert ang.max() < 1e-5, (ang.max(), iters, iters_o)  # rad; PCG vs sparse direct solve, ocml vs libm
+    assert abs(iters - iters_o) <= 1
+    eng.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("V,reach,comps", [(900, 3, 1), (3000, 4, 1), (5000, 3, 2), (6144, 5, 1)])
 def test_hip_rotation_averaging_on_sequence_graphs(V, reach, comps, capfd, monkeypatch):
     """Sparse, banded view graphs: the Jacobi-preconditioned solve runs into its cap and the solver must switch to the
