@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pgi_normal_monomials.hpp"
+
 #define PGI_DEV __device__ __forceinline__
 // coarse phases are real calls: register allocation (and spilling) is per phase, and only the
 // caller's few live values are saved around a call instead of inside the hot loops

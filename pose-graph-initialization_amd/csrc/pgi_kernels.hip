@@ -38,7 +38,6 @@ namespace pgi {
 constexpr int kMaxNW = 4;
 constexpr uint32_t kNw1Pairs = 98304, kNw2Pairs = 12288;  // launch_estimate's rule (batch sizes from which 1 / 2 wavefronts per pair pay)
 constexpr int QCAP = 40;       // models per wavefront pass (4 hypotheses x 10 roots)
-constexpr double QMAGIC = 393216.0;  // 1.5 * 2^18: summands rounded to multiples of 2^-34
 
 // Graph-cut local optimisation (prm.lo_graph_cut): the labelling context of a pair.  It lives in the workgroup's shared state,
 // written once by thread 0 and read by the (noinline) labelling code -- the fit itself carries ONE pointer to it and nothing
@@ -388,19 +387,19 @@ __device__ __noinline__ uint32_t gc_label_rows(const float4* lds, const float* x
 
 // Inlier set of model E at bound tau2 -> exact 9x9 normal matrix in loA (LDS) and the inlier
 // count, by ONE wavefront (local optimisation runs on wave 0 while the others solve hypotheses).
-// Summands are pre-rounded to 2^-34 so every summation order agrees.  Three sweeps of <= 18
-// accumulators keep the register footprint small; tri (45 doubles) is scratch for the triangle.
+// Summands are pre-rounded to 2^-34 so every summation order agrees.  The 45 entries of the upper
+// triangle are 36 distinct monomials (pgi_normal_monomials.hpp): two sweeps of 18 accumulators keep
+// the register footprint small; tri (36 doubles) is scratch for the sums.
 // (lab != nullptr: the row set is a labelling -- graph-cut local optimisation -- instead of the rows inside the bound)
 template <int LDS_PTS>
 PGI_DEV uint32_t normal_matrix_wave(const Rows<LDS_PTS>& rows, uint32_t npad, const float E[9], float tau2,
                                     double* loA, double* tri, int lane, const uint8_t* lab = nullptr) {
     uint32_t cnt = 0;
 #pragma unroll
-    for (int blk = 0; blk < 3; ++blk) {
-        constexpr int kLo[3] = {0, 17, 35}, kRow0[3] = {0, 2, 5}, kRow1[3] = {2, 5, 9}, kCnt[3] = {17, 18, 10};
-        double S[18];
+    for (int blk = 0; blk < 2; ++blk) {
+        double S[kNormalPass];
 #pragma unroll
-        for (int i = 0; i < 18; ++i) S[i] = 0.0;
+        for (int i = 0; i < kNormalPass; ++i) S[i] = 0.0;
         for (uint32_t base = 0; base < npad; base += 64) {
             const float4 p = rows.get(base + lane);
             float r2, den;
@@ -408,47 +407,25 @@ PGI_DEV uint32_t normal_matrix_wave(const Rows<LDS_PTS>& rows, uint32_t npad, co
             const bool in = lab ? (base + (uint32_t)lane < rows.n && lab[base + lane] != 0) : (r2 < tau2 * den);
             if (blk == 0) cnt += __popcll(__ballot(in));
             if (in) {
-                const double x1 = p.x, y1 = p.y, x2 = p.z, y2 = p.w;
                 double a[9];
-                a[0] = x2 * x1; a[1] = x2 * y1; a[2] = x2;
-                a[3] = y2 * x1; a[4] = y2 * y1; a[5] = y2;
-                a[6] = x1;      a[7] = y1;      a[8] = 1.0;
-                constexpr int kTri[9] = {0, 9, 17, 24, 30, 35, 39, 42, 44};
-#pragma unroll
-                for (int ii = kRow0[blk]; ii < kRow1[blk]; ++ii)
-#pragma unroll
-                    for (int jj = ii; jj < 9; ++jj) {
-                        const int k = kTri[ii] + (jj - ii) - kLo[blk];
-                        double t = a[ii] * a[jj];
-                        t = (t + QMAGIC) - QMAGIC;
-                        S[k] = S[k] + t;
-                    }
+                normal_design_row(p.x, p.y, p.z, p.w, a);
+                if (blk == 0) normal_accumulate<0>(a, S); else normal_accumulate<1>(a, S);
             }
         }
 #pragma unroll
-        for (int i = 0; i < kCnt[blk]; ++i) {
+        for (int i = 0; i < kNormalPass; ++i) {
             const double v = wave_sum_exact(S[i]);
-            if (lane == 0) tri[kLo[blk] + i] = v;
+            if (lane == 0) tri[kNormalPass * blk + i] = v;
         }
     }
     wave_sync();
-    if (lane < 45) {  // unrank lane -> (i,j), i <= j
-        int i = 0, rem = lane;
-        while (rem >= 9 - i) {
-            rem -= 9 - i;
-            ++i;
-        }
-        const int j = i + rem;
-        const double v = tri[lane];
-        loA[9 * i + j] = v;
-        loA[9 * j + i] = v;
-    }
+    if (lane < kNormalMonomials) normal_scatter(lane, tri[lane], loA);
     wave_sync();
     return cnt;
 }
 
 // Workgroup-cooperative variant (all NW wavefronts; two barriers): used for the FIRST refit after a
-// merge, where every wavefront is synchronised anyway.  partial: NW*45 doubles of dead scratch.
+// merge, where every wavefront is synchronised anyway.  partial: NW*36 doubles of dead scratch.
 template <int LDS_PTS, int NW>
 PGI_DEV uint32_t normal_matrix_wg(const Rows<LDS_PTS>& rows, uint32_t npad, const float E[9], float tau2,
                                   double* loA, double* partial, WgShared<NW>* sh, int tid) {
@@ -456,11 +433,10 @@ PGI_DEV uint32_t normal_matrix_wg(const Rows<LDS_PTS>& rows, uint32_t npad, cons
     const int lane = tid & 63, w = tid >> 6;
     uint32_t cnt = 0;
 #pragma unroll
-    for (int blk = 0; blk < 3; ++blk) {
-        constexpr int kLo[3] = {0, 17, 35}, kRow0[3] = {0, 2, 5}, kRow1[3] = {2, 5, 9}, kCnt[3] = {17, 18, 10};
-        double S[18];
+    for (int blk = 0; blk < 2; ++blk) {
+        double S[kNormalPass];
 #pragma unroll
-        for (int i = 0; i < 18; ++i) S[i] = 0.0;
+        for (int i = 0; i < kNormalPass; ++i) S[i] = 0.0;
         for (uint32_t base = 0; base < npad; base += NT) {
             const uint32_t i = base + tid;
             const float nanv = __builtin_nanf("");
@@ -470,43 +446,24 @@ PGI_DEV uint32_t normal_matrix_wg(const Rows<LDS_PTS>& rows, uint32_t npad, cons
             const bool in = r2 < tau2 * den;
             if (blk == 0) cnt += __popcll(__ballot(in));
             if (in) {
-                const double x1 = p.x, y1 = p.y, x2 = p.z, y2 = p.w;
                 double a[9];
-                a[0] = x2 * x1; a[1] = x2 * y1; a[2] = x2;
-                a[3] = y2 * x1; a[4] = y2 * y1; a[5] = y2;
-                a[6] = x1;      a[7] = y1;      a[8] = 1.0;
-                constexpr int kTri[9] = {0, 9, 17, 24, 30, 35, 39, 42, 44};
-#pragma unroll
-                for (int ii = kRow0[blk]; ii < kRow1[blk]; ++ii)
-#pragma unroll
-                    for (int jj = ii; jj < 9; ++jj) {
-                        const int k = kTri[ii] + (jj - ii) - kLo[blk];
-                        double t = a[ii] * a[jj];
-                        t = (t + QMAGIC) - QMAGIC;
-                        S[k] = S[k] + t;
-                    }
+                normal_design_row(p.x, p.y, p.z, p.w, a);
+                if (blk == 0) normal_accumulate<0>(a, S); else normal_accumulate<1>(a, S);
             }
         }
 #pragma unroll
-        for (int i = 0; i < kCnt[blk]; ++i) {
+        for (int i = 0; i < kNormalPass; ++i) {
             const double v = wave_sum_exact(S[i]);
-            if (lane == 0) partial[45 * w + kLo[blk] + i] = v;
+            if (lane == 0) partial[kNormalMonomials * w + kNormalPass * blk + i] = v;
         }
     }
     if (lane == 0) sh->wave_cnt[w] = cnt;
     __syncthreads();
-    if (tid < 45) {
+    if (tid < kNormalMonomials) {
         double v = partial[tid];
 #pragma unroll
-        for (int ww = 1; ww < NW; ++ww) v = v + partial[45 * ww + tid];
-        int i = 0, rem = tid;
-        while (rem >= 9 - i) {
-            rem -= 9 - i;
-            ++i;
-        }
-        const int j = i + rem;
-        loA[9 * i + j] = v;
-        loA[9 * j + i] = v;
+        for (int ww = 1; ww < NW; ++ww) v = v + partial[kNormalMonomials * ww + tid];
+        normal_scatter(tid, v, loA);
     }
     uint32_t total = 0;
 #pragma unroll
@@ -597,7 +554,7 @@ PGI_DEV uint32_t refit_wave0(const Rows<LDS_PTS>& rows, uint32_t n, uint32_t npa
                              uint32_t lin_pct = 0u, GcCtx* gc = nullptr) {
     double* loA = wscr0 + W_REGA + G_REGA_SZ;  // 81
     double* loV = loA + 81;                    // 81 (ends at W_REGA + 228 <= W_DOUBLES)
-    double* tri = wscr0 + G_BASIS_SZ;          // 45 doubles over basis of groups 1..2
+    double* tri = wscr0 + G_BASIS_SZ;          // 36 doubles over the basis of group 1
     float* queue0 = reinterpret_cast<float*>(wscr0 + W_REGA);
     r_score = -1;
     r_ninl = 0;

@@ -277,7 +277,7 @@ def default_params(**kw):
     return p
 
 
-def kernel_source_sha256(files=("csrc/pgi_kernels.hip", "csrc/pgi_device.hpp")):
+def kernel_source_sha256(files=("csrc/pgi_kernels.hip", "csrc/pgi_device.hpp", "csrc/pgi_normal_monomials.hpp")):
     """sha256 over the sources of the pose-estimation kernels (K1/K2/K3), in the given order.  Profile summaries under
     profiles/ record it (scripts/k1_pmc_json.py); bench.py replays their counters only while it still matches the
     sources the loaded library was built from."""

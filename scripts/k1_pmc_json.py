@@ -61,7 +61,7 @@ def main():
         "source": "rocprofv3 --kernel-trace --pmc ... (separate passes, scripts/profile_k1.sh %s); sums / dispatches; "
                   "summaries in profiles/%s_k1_rocprofv3_summary.txt" % (TAG, TAG),
         # ties these counters to the kernels that were timed: bench.py replays them only while this hash equals the hash
-        # of the sources it runs (pyposegraphbuilder._lib.kernel_source_sha256: csrc/pgi_kernels.hip + pgi_device.hpp)
+        # of the sources it runs (pyposegraphbuilder._lib.kernel_source_sha256: csrc/pgi_kernels.hip + pgi_device.hpp + pgi_normal_monomials.hpp)
         "source_sha256": open(os.path.join(OUT, "%s_k1_source_sha256.txt" % TAG)).read().strip(),
         "git_head": sys.argv[2] if len(sys.argv) > 2 else None,
         "kernel_us_trace_avg": avg_us, "dispatches": calls,
